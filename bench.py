@@ -25,6 +25,10 @@ Other configurations of BASELINE.json, same contract, one JSON line each:
 `--gpus N` without a launcher starts the N ranks itself (python -m torch.distributed.run, 127.0.0.1).
 Rank 0 writes the full detail object to bench_detail.json (`--detail-out`) and prints ONE compact JSON line (< 4 KB: the
 contract keys, roofline, cpu_baseline, parity sample, a summary per other configuration) as the last line of stdout.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, `--dump-outputs` when given, the line.
+Everything else (phase times, delivery measurements, cpu_baseline, parity sample, the `dicey hunt` runs, the other
+configurations) runs with `--full`.
 """
 import argparse
 import ctypes as C
@@ -153,6 +157,8 @@ def cap_enum_roofline(strands: float, qlen: int, distance: int, cap_ms: float) -
 
 
 CONTRACT_LINE_LIMIT = 4096  # the driver keeps a bounded tail of stdout: r04's 25.6 KB line was not parsed
+DUMP_LIMIT = 64 * 10 ** 6     # --dump-outputs: bytes of all arrays together
+DUMP_SAMPLE_MIN_ROWS = 4096  # arrays up to this many rows are always written whole
 
 
 def _short(x, n=160):
@@ -551,6 +557,54 @@ def padlock_replay(R, e, ln, armlen=20, mingc=0.4, maxgc=0.6, tmdiff=2, max_nb=2
     return acc
 
 
+def write_outputs(d: str, arrays: dict):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (integers up to 2^53 stay exact).  When all of them together exceed
+    DUMP_LIMIT, every array longer than DUMP_SAMPLE_MIN_ROWS rows keeps a sorted sample of its rows drawn with the row count as the seed:
+    arrays of equal length (the columns of one table) keep the same rows, and two runs of equal output write equal files."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        small = sum(v.nbytes for v in arrays.values() if v.shape[0] <= DUMP_SAMPLE_MIN_ROWS)
+        frac = (DUMP_LIMIT - small) * 0.99 / (total - small)
+        for k, v in arrays.items():
+            n = v.shape[0]
+            if n > DUMP_SAMPLE_MIN_ROWS:
+                rows = np.sort(np.random.default_rng(n).choice(n, max(1, int(n * frac)), replace=False))
+                arrays[k] = v[rows]
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+
+
+def dump_hunt_block(d: str, blk, nq: int, dev):
+    """The compact answer of the last timed hunt step (DG_HUNT_COMPACT, include/dicey_gpu.h), as a caller of dg_hunt_device gets it:
+    hit counts u32[nq] | qinfo u32[nq] | records u32[nhits][2 + ops_per_hit] (position, packed meta word, alignment ops), in push
+    order; hit_query is the query of every record."""
+    from dicey_amd.shard import device_bytes
+    ptr, nbytes, nhits, oph = blk if blk is not None else (None, 0, 0, 0)
+    w = device_bytes(ptr, nbytes, dev).cpu().numpy().view(np.uint32) if nbytes else np.zeros(2 * nq, dtype=np.uint32)
+    counts = w[:nq]
+    write_outputs(d, {"hit_counts": counts, "query_info": w[nq:2 * nq],
+                      "hit_query": np.repeat(np.arange(nq), counts.astype(np.int64)),
+                      "hit_records": w[2 * nq:2 * nq + nhits * (2 + oph)].reshape(nhits, 2 + oph)})
+
+
+def dump_search_result(d: str, R):
+    """The last timed `search` step's dg_search_result: per binding site (ref, pos, primer, on_for, temp, perf_temp) in push order, and
+    per primer match_temp and pflags"""
+    import dicey_amd._capi as _capi
+    n = int(R.nsites)
+    s = np.frombuffer(C.string_at(R.sites, n * C.sizeof(_capi.Site)), dtype=np.dtype(
+        {"names": ["ref", "pos", "primer", "on_for", "temp", "perf_temp"], "formats": ["<u4", "<u4", "<u4", "u1", "<f8", "<f8"],
+         "offsets": [getattr(_capi.Site, f).offset for f in ("ref", "pos", "primer", "on_for", "temp", "perf_temp")],
+         "itemsize": C.sizeof(_capi.Site)})) if n else None
+    cols = ("ref", "pos", "primer", "on_for", "temp", "perf_temp")
+    np_ = int(R.nprimers)
+    write_outputs(d, {"sites": np.stack([s[c].astype(np.float64) for c in cols], axis=1) if n else np.zeros((0, len(cols))),
+                      "match_temp": np.ctypeslib.as_array(R.match_temp, (np_,)) if np_ else np.zeros(0),
+                      "pflags": np.ctypeslib.as_array(R.pflags, (np_,)) if np_ else np.zeros(0)})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -618,6 +672,15 @@ def main():
     ap.add_argument("--dump-gather", default="",
                     help="directory: every rank writes the hit-list bytes of its last step (local_<rank>.bin) and rank 0 what the "
                          "gather delivered for every rank (gathered_<rank>.bin); used by the tests")
+    ap.add_argument("--dump-outputs", default="",
+                    help="directory: rank 0 writes what the last timed step computed, as the caller of the timed path receives it, to "
+                         "<name>.npy (float64; hunt: hit_counts, query_info, hit_query, hit_records; search: sites, match_temp, pflags; "
+                         "padlock: the per-position arrays).  Above %d MB in all, every array longer than %d rows keeps the same fixed, "
+                         "seeded sample of its rows" % (DUMP_LIMIT // 10 ** 6, DUMP_SAMPLE_MIN_ROWS))
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the phase-time pass, the delivery measurements (sustained, same batch, one in "
+                         "flight, with D2H, host to host, the `dicey hunt` runs), cpu_baseline, the full-size parity sample and the "
+                         "sub-lines of the other configurations.  A plain run sets up, warms up, times --steps steps and prints the line")
     a = ap.parse_args()
 
     # BASELINE configs[3] at its size on ONE GPU: `--config hunt_d2 --queries 10000000 --scaling strong --gpus 1` is one
@@ -714,7 +777,7 @@ def main():
                                  for r in range(world)])
                 np.save(batches_path, more)
             # the large CLI run's queries (distinct draws, 100 000 at a time), while the text is here
-            if cfg == "hunt_d1" and world == 1 and a.cli_queries > 0 and not a.no_extras and not a.no_extra_configs:
+            if cfg == "hunt_d1" and world == 1 and a.full and a.cli_queries > 0 and not a.no_extras and not a.no_extra_configs:
                 big = np.concatenate([synth_query_batch(text, 100000, a.qlen, seed=5000 + i) for i in range((a.cli_queries + 99999) // 100000)])
                 np.save(cli_big_path, big[:a.cli_queries])
         elif cfg == "search":
@@ -722,11 +785,11 @@ def main():
         else:
             meta["exons"] = [synth_exons(text, units, seed=qseed + 100 * r) for r in range(world)]
         json.dump(meta, open(meta_path, "w"))
-        if cfg == "search" and not a.no_cpu_baseline and world == 1:
+        if cfg == "search" and a.full and not a.no_cpu_baseline and world == 1:
             host_text = text.cpu().numpy().tobytes()  # the checker's amplicon sequences come from the text
         del text
         torch.cuda.empty_cache()
-    elif rank == 0 and cfg == "search" and not a.no_cpu_baseline and world == 1:
+    elif rank == 0 and cfg == "search" and a.full and not a.no_cpu_baseline and world == 1:
         text, _ = synth_genome(int(a.genome_size), 24, seed=1, device=dev, repeats=a.genome == "repeats")
         host_text = text.cpu().numpy().tobytes()
         del text
@@ -928,6 +991,8 @@ def main():
                     if R.ops_per_hit and R.nhits:  # alignment description (dicey_gpu.h): 4 bytes per unit of distance
                         parts.append(device_bytes(R.d_ops, R.nhits * R.ops_per_hit * 4, dev))
                 gather_parts(parts)
+            if a.dump_outputs:  # the compact block stays valid in HBM until the next call on this index (include/dicey_gpu.h)
+                pipe["last_block"] = (R.d_block, int(R.d_block_bytes), int(R.nhits), int(R.ops_per_hit))
             L.dg_hunt_result_free(rp)
             return res
 
@@ -953,6 +1018,8 @@ def main():
                 gather_parts([device_bytes(R.d_hits, R.nhits * 4 * (2 + R.ops_per_hit), dev)] if R.compact else
                              [device_bytes(R.d_hits, R.nhits * C.sizeof(_capi.Hit), dev)] +
                              ([device_bytes(R.d_ops, R.nhits * R.ops_per_hit * 4, dev)] if R.ops_per_hit and R.nhits else []))
+            if a.dump_outputs:  # the compact block stays valid in HBM until the next submit on its lane (include/dicey_gpu.h)
+                pipe["last_block"] = (R.d_block, int(R.d_block_bytes), int(R.nhits), int(R.ops_per_hit))
             L.dg_hunt_result_free(rp)
             return res
 
@@ -981,12 +1048,14 @@ def main():
             acc, elapsed, gathered = timed(step_pipe, flush_pipe)
         else:
             acc, elapsed, gathered = timed(step)
+        if a.dump_outputs and rank == 0:
+            dump_hunt_block(a.dump_outputs, pipe.get("last_block"), nq, dev)
         # the stages' times (HIP events between the kernels, DG_HUNT_PHASE_TIMES) are taken in a pass of their own behind the timed
         # region: every event record is a marker packet in the stream, and the timed steps run without them (the batch total and the
         # search kernel's own time — what roofline.kernel_ms is — are measured in every step)
         p_phase = _capi.HuntParams(distance, ham, 0, 1000, 10000, a.qlen, _capi.DG_HUNT_COMPACT | _capi.DG_HUNT_PHASE_TIMES)
         acc_ph = []
-        if rank == 0:
+        if rank == 0 and a.full:
             gp_saved, pipe["g"] = pipe["g"], None
             try:
                 for _ in range(max(3, min(a.steps, 10))):
@@ -1005,7 +1074,7 @@ def main():
 
         # ---------------- extras, outside the timed region (N=1): what delivery costs
         extras = {}
-        if world == 1 and nq and not a.no_extras:
+        if world == 1 and a.full and nq and not a.no_extras:
             # the headline's witness: the SAME pipeline (rotating batches, a.in_flight in flight, results left in HBM) over at least one
             # second of wall clock, drained inside the timed span — K = 20 steps of 0.19 ms are a 3.7 ms measurement
             n_sus = int(max(a.steps, min(200000, 1.15 / max(elapsed / a.steps, 1e-6))))
@@ -1025,7 +1094,7 @@ def main():
             extras["sustained"] = {"value": nq * n_sus / dts, "unit": "primers/s", "seconds": dts, "steps": n_sus, "ms_per_step": dts / n_sus * 1e3,
                                    "note": "the timed region's pipeline, unchanged, for >= 1 s: every step a complete pass over its batch, all "
                                            "steps started and drained inside the span"}
-        if world == 1 and len(dev_batches) > 1:
+        if world == 1 and a.full and len(dev_batches) > 1:
             # the replayed-batch figure of r01-r03 beside the headline: the same K steps on batch 0 only (its lines stay in the caches)
             rot["on"] = False
             for _ in range(2):
@@ -1040,7 +1109,7 @@ def main():
                                           "note": "the r01-r03 measurement: one batch replayed K times (its 310 MB of index lines are "
                                                   "re-read every step); the headline cycles through %d distinct batches" % len(dev_batches)}
             rot["on"] = True
-        if world == 1 and a.in_flight >= 2:
+        if world == 1 and a.full and a.in_flight >= 2:
             # the r01-r04a form beside the headline: one batch at a time through dg_hunt_device (rotating batches)
             for _ in range(2):
                 step()
@@ -1053,7 +1122,7 @@ def main():
                                              "kernel_ms": float(np.mean([r["ms_search_flat"] for r in acc_one])),
                                              "note": "dg_hunt_device, one batch at a time: the kernel's duration without another lane's kernels beside it"}
         pipelined = None
-        if world == 1 and not a.no_extras:
+        if world == 1 and a.full and not a.no_extras:
             for _ in range(2):
                 step(fetch=1, params=p_compact)
             torch.cuda.synchronize()
@@ -1139,7 +1208,7 @@ def main():
 
         # ---------------- cpu baseline + parity spot check at full size (rank 0, N=1 only)
         cpu = cpu_par = parity = None
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as O  # the checker / CPU port; never on the measured GPU path
             t3 = time.time()
@@ -1418,12 +1487,21 @@ def main():
                 nb = R.nsites * C.sizeof(_capi.Site)
                 sites = torch.frombuffer(bytearray(C.string_at(R.sites, nb)), dtype=torch.uint8) if nb else torch.empty(0, dtype=torch.uint8)
                 gather_parts([sites.to(dev if a.backend == "nccl" else "cpu")])
-            L.dg_search_result_free(rp)
+            if a.dump_outputs:  # the last step's result is kept for the dump, the one before goes back
+                if pipe.get("last_search") is not None:
+                    L.dg_search_result_free(pipe["last_search"])
+                pipe["last_search"] = rp
+            else:
+                L.dg_search_result_free(rp)
             return res
 
         acc, elapsed, gathered = timed(step)
+        if a.dump_outputs:
+            if rank == 0:
+                dump_search_result(a.dump_outputs, pipe["last_search"].contents)
+            L.dg_search_result_free(pipe.pop("last_search"))
         cpu = parity = None
-        if rank == 0 and world == 1 and not a.no_cpu_baseline and host_text is not None:
+        if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and host_text is not None:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as O
             if O.ref_libs() is not None:
@@ -1506,11 +1584,17 @@ def main():
             if world > 1:
                 parts = [torch.from_numpy(R[k].view(np.uint8).copy()) for k in ("arm_tm", "probe_tm", "arm_count", "arm_nbcount")]
                 gather_parts([p_.to(dev if a.backend == "nccl" else "cpu") for p_ in parts])
+            if a.dump_outputs:
+                pipe["last_padlock"] = R
             return res
 
         acc, elapsed, gathered = timed(step)
+        if a.dump_outputs:
+            if rank == 0:
+                write_outputs(a.dump_outputs, {k: v for k, v in pipe["last_padlock"].items() if isinstance(v, np.ndarray)})
+            pipe.pop("last_padlock")
         cpu = parity = None
-        if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as O
             if O.ref_libs() is not None:
@@ -1632,7 +1716,7 @@ def main():
                             O.fast_neighbors(False)
                 except Exception as e:
                     out["cli_end_to_end_10M"] = {"error": repr(e)[:300]}
-        if (world == 1 and cfg == "hunt_d1" and a.genome == "iid" and not a.no_extra_configs and not a.no_extras and not a.queries
+        if (world == 1 and a.full and cfg == "hunt_d1" and a.genome == "iid" and not a.no_extra_configs and not a.no_extras and not a.queries
                 and a.distance < 0 and a.qlen == 20):
             out["extra_configs"] = run_extra_configs(a, fm9)
             # compact top-level summaries of the sub-lines (the driver's record keeps top-level keys whole)
@@ -1691,7 +1775,7 @@ def run_extra_configs(a, fm9):
             res[name] = {"skipped": "extra_configs budget of %.0f s spent" % a.extra_budget_s}
             continue
         dpath = fm9 + ".detail_%s.json" % name
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-extra-configs", "--no-extras", "--detail-out", dpath] + args
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-extra-configs", "--no-extras", "--detail-out", dpath] + args
         if reuse:
             cmd += ["--fm9", fm9]
         t0 = time.time()

@@ -206,3 +206,25 @@ def test_cap_enum_block_is_labelled_latency_bound():
     assert r["achieved"] > 0 and 0 < r["hbm_frac_upper_bound"] < 1
     j = _line_with({"roofline": bench.rocprof_average(r, "none")})
     assert j["roofline"]["bound"] == "latency" and j["roofline"]["frac"] is None and j["roofline"]["frac_rocprof_avg"] is None
+
+
+def test_dump_outputs_stays_under_its_limit_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: float64 files, small arrays whole, large ones cut to the same seeded rows (columns of one table stay aligned),
+    at most bench.DUMP_LIMIT bytes in all, and the same files from the same arrays"""
+    import numpy as np
+    import bench
+    n = 3000000
+    arrays = {"hit_counts": np.arange(100, dtype=np.uint32), "hit_query": np.arange(n, dtype=np.int64),
+              "hit_records": np.repeat(np.arange(n, dtype=np.uint32)[:, None], 4, axis=1)}
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in arrays}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_LIMIT
+    assert np.array_equal(got["hit_counts"], np.arange(100))
+    q, r = got["hit_query"], got["hit_records"]
+    assert 0 < len(q) < n and len(q) == len(r) and np.all(np.diff(q) > 0) and np.array_equal(r[:, 3], q)
+    for k in arrays:
+        assert np.array_equal(np.load(tmp_path / "b" / (k + ".npy")), got[k])
+    bench.write_outputs(str(tmp_path / "c"), {"x": np.arange(5000, dtype=np.uint32)})   # under the limit: everything
+    assert np.array_equal(np.load(tmp_path / "c" / "x.npy"), np.arange(5000))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: `dicey hunt` end to end (process seam) on the bench genome: 100 000 queries from a FASTA file to JSON lines.
 cd "$GRAFT_REPO_ROOT"
-timeout 300 python bench.py --keep-index --steps 2 --warmup 1 --no-cpu-baseline --pipeline 1 > /tmp/b1.log 2>&1
+timeout 300 python bench.py --full --keep-index --steps 2 --warmup 1 --no-cpu-baseline --pipeline 1 > /tmp/b1.log 2>&1
 FM9=$(ls /dev/shm/dicey_bench_*.fm9 | head -1)
 python - "$FM9" <<'PY'
 import json, sys

@@ -6,13 +6,13 @@ OUT=gpurun_out/expk
 mkdir -p $OUT
 FM9=$(ls /dev/shm/dicey_bench_*.fm9 2>/dev/null | head -1)
 if [ -z "$FM9" ]; then
-  timeout 600 python bench.py --steps 1 --warmup 0 --no-extras --no-cpu-baseline --parity-queries 0 --keep-index > $OUT/build.json 2> $OUT/build.err
+  timeout 600 python bench.py --full --steps 1 --warmup 0 --no-extras --no-cpu-baseline --parity-queries 0 --keep-index > $OUT/build.json 2> $OUT/build.err
   FM9=$(ls /dev/shm/dicey_bench_*.fm9 | head -1)
 fi
 for V in ${1:-"17:18 16:18"}; do
   K=${V%%:*}; K2=${V##*:}
   for CFG in hunt_d1 hunt_d2; do
-    DICEY_KMER_K=$K DICEY_KMER_K2=$K2 timeout 300 python bench.py --fm9 $FM9 --config $CFG --steps 5 --warmup 2 --no-extras --no-cpu-baseline --parity-queries 0 \
+    DICEY_KMER_K=$K DICEY_KMER_K2=$K2 timeout 300 python bench.py --full --fm9 $FM9 --config $CFG --steps 5 --warmup 2 --no-extras --no-cpu-baseline --parity-queries 0 \
       > $OUT/${CFG}_K${K}_K2${K2}.json 2> $OUT/${CFG}_K${K}_K2${K2}.err
     python - <<PY
 import json

@@ -3,11 +3,12 @@
 # usage: tools/kstats.sh <tag> <bench args...>
 set -u
 cd "$GRAFT_REPO_ROOT"
+ROOT=$PWD
 export TMPDIR=/tmp
 TAG=$1; shift
 OUT=gpurun_out/kstats_$TAG
 rm -rf $OUT; mkdir -p $OUT
-(cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$OUT/trace -o trace --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras "$@" > $GRAFT_REPO_ROOT/$OUT/bench.json 2> $GRAFT_REPO_ROOT/$OUT/bench.err)
+(cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/trace -o trace --output-format csv -- python $ROOT/bench.py --full --no-cpu-baseline --no-extras "$@" > $ROOT/$OUT/bench.json 2> $ROOT/$OUT/bench.err)
 python - "$OUT" <<'PY'
 import csv, re, sys, os
 sys.path.insert(0, os.path.join(os.environ.get('GRAFT_REPO_ROOT', '.'), 'tools'))

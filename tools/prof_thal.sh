@@ -4,21 +4,22 @@
 # kernel trace only.  Summary -> gpurun_out/prof_thal/thal_counters.json, stamped with the sources' build_id; copy it to profiles/thal_counters.json.
 set -u
 cd "$GRAFT_REPO_ROOT"
+ROOT=$PWD
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_thal
 rm -rf $OUT; mkdir -p $OUT
 FM9=$(ls /dev/shm/dicey_bench_*iid*.fm9 2>/dev/null | head -1)
 if [ -z "$FM9" ]; then
-  timeout 600 python bench.py --steps 1 --warmup 0 --no-extras --no-cpu-baseline --no-extra-configs --parity-queries 0 --keep-index --detail-out /tmp/build_detail.json > $OUT/build.json 2> $OUT/build.err
+  timeout 600 python bench.py --full --steps 1 --warmup 0 --no-extras --no-cpu-baseline --no-extra-configs --parity-queries 0 --keep-index --detail-out /tmp/build_detail.json > $OUT/build.json 2> $OUT/build.err
   FM9=$(ls /dev/shm/dicey_bench_*iid*.fm9 | head -1)
 fi
 for CFG in search padlock; do
-  timeout 600 python bench.py --config $CFG --fm9 $FM9 --steps 2 --warmup 1 --no-cpu-baseline --no-extras --detail-out $OUT/bench_$CFG.json > $OUT/bench_line_$CFG.json 2> $OUT/bench_$CFG.err
+  timeout 600 python bench.py --full --config $CFG --fm9 $FM9 --steps 2 --warmup 1 --no-cpu-baseline --no-extras --detail-out $OUT/bench_$CFG.json > $OUT/bench_line_$CFG.json 2> $OUT/bench_$CFG.err
   i=0
   while read -r C; do
     [ -z "$C" ] && continue
     i=$((i+1))
-    (cd /tmp && timeout 900 rocprofv3 --pmc $C --kernel-trace -d $GRAFT_REPO_ROOT/$OUT/${CFG}_pmc_$i -o pmc --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --config $CFG --fm9 $FM9 --no-cpu-baseline --no-extras --steps 1 --warmup 1 --detail-out /tmp/thal_pmc_detail.json > $GRAFT_REPO_ROOT/$OUT/${CFG}_pmc_$i.json 2> $GRAFT_REPO_ROOT/$OUT/${CFG}_pmc_$i.err)
+    (cd /tmp && timeout 900 rocprofv3 --pmc $C --kernel-trace -d $ROOT/$OUT/${CFG}_pmc_$i -o pmc --output-format csv -- python $ROOT/bench.py --full --config $CFG --fm9 $FM9 --no-cpu-baseline --no-extras --steps 1 --warmup 1 --detail-out /tmp/thal_pmc_detail.json > $ROOT/$OUT/${CFG}_pmc_$i.json 2> $ROOT/$OUT/${CFG}_pmc_$i.err)
   done <<LIST
 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES
 SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE

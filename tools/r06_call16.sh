@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/r06
 mkdir -p $O
-timeout 900 python bench.py --keep-index --steps 2 --warmup 1 --no-extra-configs --no-cpu-baseline --parity-queries 0 --cli-queries 0 > $O/c16_base.line 2> $O/c16_base.err
+timeout 900 python bench.py --full --keep-index --steps 2 --warmup 1 --no-extra-configs --no-cpu-baseline --parity-queries 0 --cli-queries 0 > $O/c16_base.line 2> $O/c16_base.err
 FM9=$(ls /dev/shm/dicey_bench_*iid*.fm9 | head -1)
 V=$GRAFT_REPO_ROOT/dicey_amd/variants/libdiceygpu_exp.so
 (echo "== unwinding exit"; timeout 900 python tools/cli_10m.py $FM9 10000000 2 DICEY_NO_QUICK_EXIT=1

@@ -8,11 +8,11 @@ timeout 1200 python -m pytest tests/test_gpu_parity.py tests/test_gpu_cli.py -m 
 tail -3 $O/pytest_c17.log
 V=$GRAFT_REPO_ROOT/dicey_amd/variants
 B="--steps 20 --warmup 8 --no-extra-configs --no-cpu-baseline --parity-queries 300 --cli-queries 0 --no-extras"
-timeout 900 python bench.py $B --keep-index --detail-out $O/np_base.json > $O/np_base.line 2> $O/np_base.err
+timeout 900 python bench.py --full $B --keep-index --detail-out $O/np_base.json > $O/np_base.line 2> $O/np_base.err
 FM9=$(ls /dev/shm/dicey_bench_*iid*.fm9 | head -1)
-DICEY_LIB=$V/libdiceygpu_exp.so DICEY_NO_PRE5=1 timeout 600 python bench.py --fm9 $FM9 $B --detail-out $O/np_nopre5.json > $O/np_nopre5.line 2> $O/np_nopre5.err
-timeout 600 python bench.py --fm9 $FM9 $B --config hunt_d2 --detail-out $O/np_d2.json > $O/np_d2.line 2> $O/np_d2.err
-DICEY_LIB=$V/libdiceygpu_exp.so DICEY_NO_PRE5=1 timeout 600 python bench.py --fm9 $FM9 $B --config hunt_d2 --detail-out $O/np_d2_nopre5.json > $O/np_d2_nopre5.line 2> $O/np_d2_nopre5.err
+DICEY_LIB=$V/libdiceygpu_exp.so DICEY_NO_PRE5=1 timeout 600 python bench.py --full --fm9 $FM9 $B --detail-out $O/np_nopre5.json > $O/np_nopre5.line 2> $O/np_nopre5.err
+timeout 600 python bench.py --full --fm9 $FM9 $B --config hunt_d2 --detail-out $O/np_d2.json > $O/np_d2.line 2> $O/np_d2.err
+DICEY_LIB=$V/libdiceygpu_exp.so DICEY_NO_PRE5=1 timeout 600 python bench.py --full --fm9 $FM9 $B --config hunt_d2 --detail-out $O/np_d2_nopre5.json > $O/np_d2_nopre5.line 2> $O/np_d2_nopre5.err
 python - <<'PY'
 import json
 for n in ("base", "nopre5", "d2", "d2_nopre5"):

@@ -8,12 +8,12 @@ timeout 1500 python -m pytest tests/test_gpu_locate_topk.py tests/test_gpu_parit
 tail -5 $O/pytest_c18.log
 V=$GRAFT_REPO_ROOT/dicey_amd/variants
 B="--steps 20 --warmup 8 --no-extra-configs --no-cpu-baseline --parity-queries 1000 --cli-queries 0"
-timeout 900 python bench.py $B --keep-index --detail-out $O/dc_on.json > $O/dc_on.line 2> $O/dc_on.err
+timeout 900 python bench.py --full $B --keep-index --detail-out $O/dc_on.json > $O/dc_on.line 2> $O/dc_on.err
 FM9=$(ls /dev/shm/dicey_bench_*iid*.fm9 | head -1)
-DICEY_LIB=$V/libdiceygpu_exp.so DICEY_NO_DIRECT_CTX=1 timeout 600 python bench.py --fm9 $FM9 $B --detail-out $O/dc_off.json > $O/dc_off.line 2> $O/dc_off.err
-timeout 600 python bench.py --fm9 $FM9 $B --detail-out $O/dc_on2.json > $O/dc_on2.line 2> $O/dc_on2.err
-DICEY_LIB=$V/libdiceygpu_exp.so DICEY_NO_DIRECT_CTX=1 timeout 600 python bench.py --fm9 $FM9 $B --detail-out $O/dc_off2.json > $O/dc_off2.line 2> $O/dc_off2.err
-timeout 600 python bench.py --fm9 $FM9 $B --n-frac 0.05 --detail-out $O/dc_nmix.json > $O/dc_nmix.line 2> $O/dc_nmix.err
+DICEY_LIB=$V/libdiceygpu_exp.so DICEY_NO_DIRECT_CTX=1 timeout 600 python bench.py --full --fm9 $FM9 $B --detail-out $O/dc_off.json > $O/dc_off.line 2> $O/dc_off.err
+timeout 600 python bench.py --full --fm9 $FM9 $B --detail-out $O/dc_on2.json > $O/dc_on2.line 2> $O/dc_on2.err
+DICEY_LIB=$V/libdiceygpu_exp.so DICEY_NO_DIRECT_CTX=1 timeout 600 python bench.py --full --fm9 $FM9 $B --detail-out $O/dc_off2.json > $O/dc_off2.line 2> $O/dc_off2.err
+timeout 600 python bench.py --full --fm9 $FM9 $B --n-frac 0.05 --detail-out $O/dc_nmix.json > $O/dc_nmix.line 2> $O/dc_nmix.err
 python - <<'PY'
 import json
 for n in ("on", "off", "on2", "off2", "nmix"):

@@ -1,17 +1,18 @@
 #!/bin/bash
 # r06: locate tests + index --verify test, repeats-genome configuration (default and DICEY_VERIFY_CH=4), kernel stats
 cd "$GRAFT_REPO_ROOT"
+ROOT=$PWD
 export TMPDIR=/tmp
 O=gpurun_out/r06
 T=${1:-c}
 mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_locate_topk.py tests/test_gpu_cli.py::test_index_verify_accepts_its_file_and_refuses_foreign_ones tests/test_gpu_parity.py -m gpu -x -q > $O/pytest_$T.log 2>&1
 tail -4 $O/pytest_$T.log
-timeout 900 python bench.py --genome repeats --steps 30 --warmup 8 --no-extras --no-extra-configs --cpu-seconds 3 --parity-queries 300 --keep-index \
+timeout 900 python bench.py --full --genome repeats --steps 30 --warmup 8 --no-extras --no-extra-configs --cpu-seconds 3 --parity-queries 300 --keep-index \
   --detail-out $O/repeats_detail_$T.json > $O/repeats_$T.json 2> $O/repeats_$T.err
 FM9=$(ls /dev/shm/dicey_bench_*repeats*.fm9 | head -1)
 for CH in 4 2; do
-DICEY_VERIFY_CH=$CH timeout 600 python bench.py --genome repeats --fm9 $FM9 --steps 30 --warmup 8 --no-extras --no-extra-configs --no-cpu-baseline --parity-queries 0 \
+DICEY_VERIFY_CH=$CH timeout 600 python bench.py --full --genome repeats --fm9 $FM9 --steps 30 --warmup 8 --no-extras --no-extra-configs --no-cpu-baseline --parity-queries 0 \
   --detail-out $O/repeats_detail_${T}_ch$CH.json > $O/repeats_${T}_ch$CH.json 2> $O/repeats_${T}_ch$CH.err
 done
 python - $T <<'PY'
@@ -24,7 +25,7 @@ for sfx in ("", "_ch4", "_ch2"):
     except Exception as e:
         print(sfx, e)
 PY
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$O/trace_rep_$T -o trace --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --genome repeats --fm9 $FM9 --no-cpu-baseline --no-extras --no-extra-configs --parity-queries 0 --steps 12 --warmup 4 --detail-out $GRAFT_REPO_ROOT/$O/rep_traced_detail_$T.json > $GRAFT_REPO_ROOT/$O/rep_traced_$T.json 2> $GRAFT_REPO_ROOT/$O/rep_trace_$T.err)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $ROOT/$O/trace_rep_$T -o trace --output-format csv -- python $ROOT/bench.py --full --genome repeats --fm9 $FM9 --no-cpu-baseline --no-extras --no-extra-configs --parity-queries 0 --steps 12 --warmup 4 --detail-out $ROOT/$O/rep_traced_detail_$T.json > $ROOT/$O/rep_traced_$T.json 2> $ROOT/$O/rep_trace_$T.err)
 python - $T <<'PY'
 import csv, sys, os
 sys.path.insert(0, "tools")

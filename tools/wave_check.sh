@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: wave thal kernel vs sequential kernel on the 3.1 Gb search workload (every hit's Tm and position), timing, tests.
 cd "$GRAFT_REPO_ROOT"
-timeout 200 python bench.py --keep-index --steps 2 --warmup 1 --no-cpu-baseline > /tmp/b1.log 2>&1
+timeout 200 python bench.py --full --keep-index --steps 2 --warmup 1 --no-cpu-baseline > /tmp/b1.log 2>&1
 FM9=$(ls /dev/shm/dicey_bench_*.fm9 | head -1)
 if [ "${1:-}" != "fast" ]; then
 DICEY_DEBUG_DUMP_RAW=/tmp/s.raw DICEY_DEBUG_THAL_REDO=1 timeout 300 python tools/bench_search.py --no-cpu --fm9 $FM9 > /dev/null 2>&1
