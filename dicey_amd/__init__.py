@@ -145,6 +145,56 @@ class FmIndex:
         finally:
             self._L.dg_locations_free(lp)
 
+    def _map(self, k, forward_only, max_count):
+        prm = _capi.MapParams(k, 1 if forward_only else 0, max_count, 0)
+        m = C.c_void_p()
+        _capi.check(self._L, self._L.dg_mappability(self._h, C.byref(prm), C.byref(m)))
+        return m
+
+    def mappability(self, k: int = 100, forward_only: bool = False, max_count: int = 0, stats: Optional[dict] = None):
+        """Exact-match k-mer uniqueness of every text position (include/dicey_gpu.h dg_mappability): numpy uint32 array of n-1
+        values, value[p] = count(w) + count(revcomp(w)) for the k-mer w at p (count(w) alone with forward_only), 0 where no
+        k-mer of A/C/G/T starts; min(value, max_count) when max_count > 0.  `stats`, when given, receives the phase times."""
+        import numpy as np
+        m = self._map(k, forward_only, max_count)
+        try:
+            st = _capi.MapStats()
+            _capi.check(self._L, self._L.dg_map_stats(m, C.byref(st)))
+            out = np.zeros(st.n - 1, dtype=np.uint32)
+            _capi.check(self._L, self._L.dg_map_values(m, 0, st.n - 1, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+            if stats is not None:
+                stats.update({f: getattr(st, f) for f, _ in _capi.MapStats._fields_ if f != "reserved"})
+            return out
+        finally:
+            self._L.dg_map_free(m)
+
+    def mappability_runs(self, k: int = 100, forward_only: bool = False, max_count: int = 0, lo: int = 0, hi: Optional[int] = None):
+        """The same values as maximal runs of equal non-zero values inside text positions [lo, hi) (hi = n-1 when None): numpy
+        arrays (start uint64, length uint32, value uint32); a run is cut at lo and hi."""
+        m = self._map(k, forward_only, max_count)
+        try:
+            if hi is None:
+                st = _capi.MapStats()
+                _capi.check(self._L, self._L.dg_map_stats(m, C.byref(st)))
+                hi = st.n - 1
+            return self._map_runs(m, lo, hi)
+        finally:
+            self._L.dg_map_free(m)
+
+    def _map_runs(self, m, lo, hi):
+        import numpy as np
+        nr = C.c_uint64()
+        s, ln, v = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+        _capi.check(self._L, self._L.dg_map_runs(m, lo, hi, C.byref(nr), C.byref(s), C.byref(ln), C.byref(v)))
+        try:
+            n = nr.value
+            return (np.ctypeslib.as_array(s, (n,)).copy() if n else np.zeros(0, np.uint64),
+                    np.ctypeslib.as_array(ln, (n,)).copy() if n else np.zeros(0, np.uint32),
+                    np.ctypeslib.as_array(v, (n,)).copy() if n else np.zeros(0, np.uint32))
+        finally:
+            for p in (s, ln, v):
+                self._L.dg_buffer_free(C.cast(p, C.c_void_p))
+
     def extract(self, ranges: Sequence[tuple]) -> List[bytes]:
         n = len(ranges)
         lo = (C.c_uint64 * max(1, n))(*[r[0] for r in ranges])

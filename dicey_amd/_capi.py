@@ -81,6 +81,16 @@ class Locations(C.Structure):
     _fields_ = [("npat", C.c_size_t), ("off", C.POINTER(C.c_uint64)), ("pos", C.POINTER(C.c_uint64))]
 
 
+class MapParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("forward_only", C.c_int32), ("max_count", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MapStats(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("k", C.c_uint32), ("reserved", C.c_uint32), ("ms_valid", C.c_double), ("ms_forward", C.c_double),
+                ("ms_reverse", C.c_double), ("ms_scatter", C.c_double), ("ms_total", C.c_double), ("rev_steps", C.c_uint64),
+                ("transient_bytes", C.c_uint64)]
+
+
 # every symbol include/dicey_gpu.h declares; tests/test_capi_symbols.py checks the list against the header
 class PadlockParams(C.Structure):
     _fields_ = [("armlen", C.c_uint32), ("distance", C.c_uint32), ("hamming", C.c_int32), ("tmdiff", C.c_uint32),
@@ -100,7 +110,8 @@ SYMBOLS = ["dg_index_open", "dg_index_close", "dg_index_stats", "dg_count", "dg_
            "dg_thal_open", "dg_thal_close", "dg_thal_batch", "dg_search_sites", "dg_search_result_free",
            "dg_neighborhood_count", "dg_padlock_scan", "dg_padlock_result_free", "dg_index_share",
            "dg_neighbors", "dg_buffer_free", "dg_hit_rows", "dg_hunt_rows", "dg_hunt_submit", "dg_hunt_wait", "dg_hunt_device_submit",
-           "dg_chit_unpack", "dg_normalize_query", "dg_hunt_expand", "dg_index_stream", "dg_fm9_check"]
+           "dg_chit_unpack", "dg_normalize_query", "dg_hunt_expand", "dg_index_stream", "dg_fm9_check",
+           "dg_mappability", "dg_map_values", "dg_map_runs", "dg_map_device_values", "dg_map_stats", "dg_map_free"]
 
 _lib = None
 
@@ -167,6 +178,14 @@ def load(path=None):
     L.dg_neighbors.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(vp), u64p, C.POINTER(C.c_int)]
     L.dg_buffer_free.argtypes = [vp]
     L.dg_buffer_free.restype = None
+    L.dg_mappability.argtypes = [vp, C.POINTER(MapParams), C.POINTER(vp)]
+    L.dg_map_values.argtypes = [vp, C.c_uint64, C.c_uint64, u32p]
+    L.dg_map_runs.argtypes = [vp, C.c_uint64, C.c_uint64, u64p, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(u32p)]
+    L.dg_map_device_values.argtypes = [vp]
+    L.dg_map_device_values.restype = vp
+    L.dg_map_stats.argtypes = [vp, C.POINTER(MapStats)]
+    L.dg_map_free.argtypes = [vp]
+    L.dg_map_free.restype = None
     if path is None:
         _lib = L
     return L

@@ -13,7 +13,7 @@
 
 namespace {
 
-const char* kVersion = "0.5.1";  // src/version.h:8 — goes into meta.version
+[[maybe_unused]] const char* kVersion = "0.5.1";  // src/version.h:8 — goes into meta.version
 
 // ------------------------------------------------------------------------------------------------ small utilities
 inline bool file_nonempty(const std::string& p) {

@@ -1,7 +1,7 @@
 // `dicey` host binary for the MI355X search path: keeps the command line and the JSON of the reference's
 // `dicey hunt` (reference src/dicey.cpp:35-76 dispatch, src/hunter.h:177-447) and calls the HIP kernels through the
 // C ABI of libdiceygpu.so.  `dicey index` is provided as well (src/index.h:34-141) so that a genome can be prepared
-// without the reference binary; `search` and `padlock` (padlock.cpp) ride on the same library; chop/mappability are out of scope.
+// without the reference binary; `search`, `padlock` (padlock.cpp) and `mappability` (mappability.cpp) ride on the same library; chop is out of scope.
 //
 // Host-side work that must stay on the host for bit-identical output: the hit vector arrives in the
 // reference's push order and is sorted with libstdc++ std::sort under the reference's comparator (hunter.h:63-65,440).
@@ -38,6 +38,7 @@
 #include "dtoa.hpp"
 
 int padlock_main(int argc, char** argv);  // padlock.cpp
+int mappability_main(int argc, char** argv);  // mappability.cpp
 
 namespace {
 
@@ -1457,8 +1458,9 @@ void display_usage() {  // dicey.cpp:19-33 (only the subcommands this build carr
   std::cout << "    hunt         search DNA sequences (MI355X search path)" << std::endl;
   std::cout << "    search       in-silico PCR (MI355X search path)" << std::endl;
   std::cout << "    padlock      padlock probe design (MI355X search path)" << std::endl;
+  std::cout << "    mappability  exact-match k-mer uniqueness track (MI355X search path)" << std::endl;
   std::cout << std::endl;
-  std::cout << "chop and mappability are not part of this build; use the reference binary for them." << std::endl;
+  std::cout << "chop is not part of this build." << std::endl;
   std::cout << std::endl;
 }
 
@@ -1495,6 +1497,7 @@ int main(int argc, char** argv) {
   if (cmd == "index") return indexer(argc - 1, argv + 1);
   if (cmd == "search") return silica(argc - 1, argv + 1);
   if (cmd == "padlock") return padlock_main(argc - 1, argv + 1);
+  if (cmd == "mappability") return mappability_main(argc - 1, argv + 1);
   std::cerr << "Unrecognized command " << cmd << std::endl;
   return 1;
 }

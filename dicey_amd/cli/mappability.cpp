@@ -1,0 +1,265 @@
+// `dicey mappability`: a bedGraph of exact-match k-mer uniqueness over the indexed genome (include/dicey_gpu.h dg_mappability).
+// Not upstream dicey's chop + aligner + mappability pipeline: the value of a position is the number of occurrences of the k-mer that
+// starts there, on both strands, counted on the FM-index in HBM.  The device hands over runs of equal values per position chunk;
+// the host formats the chunks on several threads, compresses them (-o) into concatenated gzip members and writes them in order.
+#include <zlib.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <iostream>
+#include <thread>
+
+#include "../../include/dicey_gpu.h"
+#include "cli_common.hpp"
+
+int mappability_main(int argc, char** argv);
+
+namespace {
+
+const OptSpec kMapOpts[] = {{"help", '?', false},  {"genome", 'g', true},  {"kmer", 'k', true},
+                            {"forward", 'f', false}, {"maxcount", 'c', true}, {"outfile", 'o', true}};
+
+void map_usage() {
+  std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz" << std::endl;
+  std::cout << "Generic options:\n"
+               "  -? [ --help ]                      show help message\n"
+               "  -g [ --genome ] arg                genome file (indexed with dicey index: <genome stem>.fm9)\n"
+               "  -k [ --kmer ] arg (=100)           k-mer length (10..1000)\n"
+               "  -f [ --forward ]                   forward strand only\n"
+               "  -c [ --maxcount ] arg (=0)         write min(value, maxcount); 0 = exact values\n"
+               "  -o [ --outfile ] arg               gzipped output file (default: plain text on stdout)\n"
+               "\n"
+               "Output: bedGraph lines name, start, end, value (0-based, end exclusive) of maximal runs of equal values, where the value\n"
+               "of a k-mer start position is the number of occurrences of that k-mer plus those of its reverse complement in the\n"
+               "genome (forward only: the k-mer alone; a reverse-complement palindrome counts twice).  Positions whose k-mer holds a\n"
+               "character other than A/C/G/T or runs past the sequence end have no line.\n"
+               "\n";
+}
+
+int bail(const std::string& m) {
+  std::cerr << m << std::endl;
+  return 1;
+}
+
+// one gzip member of `data` (deflate level 1): the chunks of a file are members of their own, which gzip -dc reads in a row
+bool gzip_member(const std::string& data, std::string& out) {
+  z_stream zs;
+  std::memset(&zs, 0, sizeof zs);
+  if (deflateInit2(&zs, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+  static const unsigned char hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
+  out.assign((const char*)hdr, 10);
+  const size_t bound = deflateBound(&zs, data.size());
+  out.resize(10 + bound + 8);
+  zs.next_in = (Bytef*)data.data();
+  zs.avail_in = (uInt)data.size();
+  zs.next_out = (Bytef*)&out[10];
+  zs.avail_out = (uInt)bound;
+  const int rc = deflate(&zs, Z_FINISH);
+  const size_t used = zs.total_out;
+  deflateEnd(&zs);
+  if (rc != Z_STREAM_END) return false;
+  const uint32_t crc = (uint32_t)crc32(0L, (const Bytef*)data.data(), (uInt)data.size()), isz = (uint32_t)data.size();
+  std::memcpy(&out[10 + used], &crc, 4);
+  std::memcpy(&out[10 + used + 4], &isz, 4);
+  out.resize(10 + used + 8);
+  return true;
+}
+
+struct Piece {  // the runs of positions [a, b) of one sequence
+  uint32_t seq = 0;
+  uint64_t a = 0, b = 0;
+  std::vector<uint64_t> start;
+  std::vector<uint32_t> len, value;
+};
+
+}  // namespace
+
+int mappability_main(int argc, char** argv) {
+  Parsed p = parse_options(argc, argv, kMapOpts, sizeof kMapOpts / sizeof kMapOpts[0]);
+  if (!p.error.empty()) {
+    std::cerr << "Error: " << p.error << std::endl;
+    map_usage();
+    return -1;
+  }
+  std::string genome, outfile;
+  bool help = false, have_genome = false, forward = false;
+  long long k = 100, maxcount = 0;
+  for (auto& kv : p.kv) {
+    if (kv.first == "help") help = true;
+    else if (kv.first == "genome") { genome = kv.second; have_genome = true; }
+    else if (kv.first == "kmer") k = std::strtoll(kv.second.c_str(), nullptr, 10);
+    else if (kv.first == "forward") forward = true;
+    else if (kv.first == "maxcount") maxcount = std::strtoll(kv.second.c_str(), nullptr, 10);
+    else if (kv.first == "outfile") outfile = kv.second;
+  }
+  if (help || !have_genome || !p.positional.empty()) {
+    map_usage();
+    return -1;
+  }
+  if (k < 10 || k > 1000) return bail("Error: k-mer length " + std::to_string(k) + " outside 10..1000!");
+  if (maxcount < 0 || maxcount > 0xFFFFFFFFll) return bail("Error: maxcount " + std::to_string(maxcount) + " outside 0..4294967295!");
+  if (!file_nonempty(genome)) return bail("Error: Genome does not exist!");
+  std::vector<uint32_t> seqlen;
+  std::vector<std::string> seqname;
+  if (!seq_len_name(genome, seqlen, seqname)) return bail("Error: Could not retrieve sequence lengths!");
+  const std::string fm9 = strip_last_extension(genome) + ".fm9";
+  if (!file_nonempty(fm9)) return bail("Error: Index " + fm9 + " does not exist (dicey index -o " + fm9 + " " + genome + ")!");
+  const char* de = std::getenv("DICEY_DEVICE");
+  const int device = de ? std::atoi(de) : 0;
+  dg_index* ix = nullptr;
+  if (dg_index_open(fm9.c_str(), device, DG_OPEN_COMPACT | DG_OPEN_NO_PRE5, &ix) != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
+  struct IxCloser {
+    dg_index* ix;
+    ~IxCloser() { dg_index_close(ix); }
+  } ixc{ix};
+  dg_index_stats_t ist;
+  if (dg_index_stats(ix, &ist) != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
+  uint64_t total = 1;
+  for (uint32_t l : seqlen) total += l;  // each length + its '\n', then the sentinel
+  if (total != ist.n)
+    return bail("Error: the sequence lengths of " + genome + " (" + std::to_string(total - 1) + " characters with separators) do not match the index " +
+                fm9 + " (" + std::to_string(ist.n - 1) + ")!");
+  dg_map_params mp = {(uint32_t)k, forward ? 1 : 0, (uint32_t)maxcount, 0u};
+  dg_map* m = nullptr;
+  if (dg_mappability(ix, &mp, &m) != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
+  struct MapFreer {
+    dg_map* m;
+    ~MapFreer() { dg_map_free(m); }
+  } mf{m};
+
+  FILE* fo = stdout;
+  if (!outfile.empty()) {
+    fo = std::fopen(outfile.c_str(), "wb");
+    if (!fo) return bail("Error: cannot open " + outfile + " for writing!");
+  }
+  // pieces of at most PIECE positions, in FASTA order; a run that crosses a piece edge is carried into the next piece of its sequence
+  // (DICEY_MAP_PIECE: a smaller piece, so that tests put piece edges inside runs of a small genome)
+  uint64_t PIECE = 1ull << 22;
+  if (const char* e = std::getenv("DICEY_MAP_PIECE")) PIECE = std::max<uint64_t>(1, std::strtoull(e, nullptr, 10));
+  std::vector<Piece> jobs;
+  {
+    uint64_t off = 0;
+    for (uint32_t s = 0; s < seqlen.size(); ++s) {
+      const uint64_t len = seqlen[s] - 1;
+      for (uint64_t a = 0; a < len; a += PIECE) {
+        Piece pc;
+        pc.seq = s;
+        pc.a = off + a;
+        pc.b = off + std::min(len, a + PIECE);
+        jobs.push_back(std::move(pc));
+      }
+      off += seqlen[s];
+    }
+  }
+  unsigned nthr = std::thread::hardware_concurrency();
+  if (const char* e = std::getenv("OMP_NUM_THREADS")) nthr = (unsigned)std::max(1, std::atoi(e));
+  nthr = std::max(1u, std::min(nthr, 16u));
+  std::vector<uint64_t> seq_off(seqlen.size());
+  for (size_t s = 0, o = 0; s < seqlen.size(); o += seqlen[s], ++s) seq_off[s] = o;
+  bool have_carry = false;
+  uint64_t carry_start = 0;
+  uint32_t carry_len = 0, carry_val = 0;
+  bool ok = true, wrote = false;
+  std::string err;
+  for (size_t j0 = 0; j0 < jobs.size() && ok; j0 += nthr) {
+    const size_t j1 = std::min(jobs.size(), j0 + nthr);
+    for (size_t j = j0; j < j1; ++j) {  // runs off the device (one call per piece), carries settled in order
+      Piece& pc = jobs[j];
+      uint64_t nr = 0;
+      uint64_t* s = nullptr;
+      uint32_t *l = nullptr, *v = nullptr;
+      if (dg_map_runs(m, pc.a, pc.b, &nr, &s, &l, &v) != DG_OK) {
+        err = std::string("dicey: ") + dg_last_error();
+        ok = false;
+        break;
+      }
+      pc.start.assign(s, s + nr);
+      pc.len.assign(l, l + nr);
+      pc.value.assign(v, v + nr);
+      dg_buffer_free(s);
+      dg_buffer_free(l);
+      dg_buffer_free(v);
+      if (have_carry) {
+        if (!pc.start.empty() && pc.start[0] == pc.a && pc.value[0] == carry_val && carry_start + carry_len == pc.a) {
+          pc.start[0] = carry_start;
+          pc.len[0] += carry_len;
+        } else {
+          pc.start.insert(pc.start.begin(), carry_start);
+          pc.len.insert(pc.len.begin(), carry_len);
+          pc.value.insert(pc.value.begin(), carry_val);
+        }
+        have_carry = false;
+      }
+      const bool seq_goes_on = j + 1 < jobs.size() && jobs[j + 1].seq == pc.seq;
+      if (seq_goes_on && !pc.start.empty() && pc.start.back() + pc.len.back() == pc.b) {
+        have_carry = true;
+        carry_start = pc.start.back();
+        carry_len = pc.len.back();
+        carry_val = pc.value.back();
+        pc.start.pop_back();
+        pc.len.pop_back();
+        pc.value.pop_back();
+      }
+    }
+    if (!ok) break;
+    std::vector<std::string> text(j1 - j0), packed(j1 - j0);
+    std::vector<char> good(j1 - j0, 1);
+    auto work = [&](size_t t) {
+      const Piece& pc = jobs[j0 + t];
+      const std::string& name = seqname[pc.seq];
+      const uint64_t so = seq_off[pc.seq];
+      std::string& o = text[t];
+      o.reserve(pc.start.size() * (name.size() + 24));
+      for (size_t r = 0; r < pc.start.size(); ++r) {
+        o += name;
+        o.push_back('\t');
+        uint_append(o, pc.start[r] - so);
+        o.push_back('\t');
+        uint_append(o, pc.start[r] - so + pc.len[r]);
+        o.push_back('\t');
+        uint_append(o, pc.value[r]);
+        o.push_back('\n');
+      }
+      if (!outfile.empty() && !o.empty()) good[t] = gzip_member(o, packed[t]);
+    };
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < j1 - j0; ++t) th.emplace_back(work, t);
+    for (auto& x : th) x.join();
+    for (size_t t = 0; t < j1 - j0 && ok; ++t) {
+      if (!good[t]) {
+        err = "Error: compression failed!";
+        ok = false;
+        break;
+      }
+      const std::string& w = outfile.empty() ? text[t] : packed[t];
+      wrote |= !w.empty();
+      if (!w.empty() && std::fwrite(w.data(), 1, w.size(), fo) != w.size()) {
+        err = "Error: short write to " + (outfile.empty() ? std::string("stdout") : outfile) + "!";
+        ok = false;
+      }
+    }
+    for (size_t j = j0; j < j1; ++j) {
+      std::vector<uint64_t>().swap(jobs[j].start);
+      std::vector<uint32_t>().swap(jobs[j].len);
+      std::vector<uint32_t>().swap(jobs[j].value);
+    }
+  }
+  if (ok && !wrote && !outfile.empty()) {  // no run at all: still a valid (empty) gzip file
+    std::string empty;
+    if (!gzip_member(std::string(), empty) || std::fwrite(empty.data(), 1, empty.size(), fo) != empty.size()) {
+      err = "Error: short write to " + outfile + "!";
+      ok = false;
+    }
+  }
+  if (fo != stdout) {
+    if (std::fclose(fo) != 0 && ok) {
+      err = "Error: cannot finish writing " + outfile + "!";
+      ok = false;
+    }
+  } else if (std::fflush(stdout) != 0 && ok) {
+    err = "Error: short write to stdout!";
+    ok = false;
+  }
+  if (!ok) return bail(err);
+  return 0;
+}

@@ -1,0 +1,445 @@
+// `dicey mappability`: exact-match k-mer uniqueness of every text position, computed on the resident index.
+//
+// value(p) = count(w) + count(revcomp(w)) for w = T[p, p+k) when w lies inside the text and holds only A/C/G/T, else 0
+// (count = sdsl::count, overlapping occurrences included; a reverse-complement palindrome counts twice per occurrence, the
+// both-strand total `padlock` uses).  Phases, all on the index's stream, handing data over only at kernel boundaries:
+//   1. valid bitmap   k_acgt_bits (1 bit per position: A/C/G/T) -> k_valid_bits (the run of A/C/G/T from p is >= k long)
+//   2. forward counts suffixes with equal k-prefixes are adjacent in the suffix array: k_fwd_boundaries marks, per rank, where
+//                     a group of equal k-mers starts (one comparison of two neighbouring suffixes); a max-scan gives every rank
+//                     its group's first rank, a min-scan over the reversed ranks its group's last one (rocprim, as build.hip)
+//   3. reverse strand k_heads: one backward search of revcomp(w) per group head (K-mer table first, left at the first empty
+//                     interval); the head's slot of the start array then holds the group's total
+//   4. scatter        k_scatter: every rank reads its head's total (a broadcast in rank order) and writes it at SA[i]
+// Transient HBM: the start array (4n) and three bitmaps (3n/8) beside the result (4n), which the end scan uses first.
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include <algorithm>
+
+#include "devfm.hpp"
+#include "index_internal.hpp"
+
+struct dg_map {
+  int device = 0;
+  hipStream_t stream = nullptr;  // own stream: the map may be read after its index handle has moved on to other work
+  uint64_t n = 0;                // index n; values cover positions [0, n-1)
+  uint32_t* out = nullptr;       // u32[n] (the entry at n-1, the sentinel, is 0)
+  dg_map_stats_t st{};
+  dg::DevBuf run_flags, run_pos, run_val, run_cnt;  // dg_map_runs workspaces (grow-only)
+  ~dg_map() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (out) dg::big_free(out, stream);
+    run_flags.release();
+    run_pos.release();
+    run_val.release();
+    run_cnt.release();
+    if (stream) {
+      (void)hipStreamSynchronize(stream);
+      (void)hipStreamDestroy(stream);
+    }
+  }
+};
+
+namespace dg {
+
+__host__ __device__ inline bool bit_at(const u64* b, u64 i) { return (b[i >> 6] >> (i & 63)) & 1ULL; }
+
+// 8 text bytes from any position (little endian: byte p in bits 0-7); the text buffer has 64 bytes of slack behind n
+DG_DEV u64 text8(const u8* t, u64 p) {
+  const u64* w = reinterpret_cast<const u64*>(t + (p & ~7ULL));
+  const u32 s = (u32)(p & 7) * 8;
+  const u64 lo = w[0];
+  return s ? (lo >> s) | (w[1] << (64 - s)) : lo;
+}
+// 2-bit code of an A/C/G/T byte: A 0x41 -> 0, C 0x43 -> 1, G 0x47 -> 2, T 0x54 -> 3
+DG_DEV u32 acgt_code(u32 b) { return ((b >> 1) ^ (b >> 2)) & 3u; }
+
+// bit j of word w = T[64w + j] is A/C/G/T (positions >= n, the sentinel and the padding words are 0)
+__global__ void k_acgt_bits(const u8* text, u64 n, u64* acgt, u64 nw) {
+  const u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nw) return;
+  u64 m = 0;
+  const u64 p0 = w * 64;
+  if (p0 < n) {
+    const uint4* q = reinterpret_cast<const uint4*>(text + p0);
+#pragma unroll
+    for (u32 c = 0; c < 4; ++c) {
+      const uint4 v = q[c];
+      const u32 wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (u32 j = 0; j < 16; ++j) {
+        const u32 b = (wd[j >> 2] >> (8 * (j & 3))) & 255u;
+        const bool ok = b == 'A' || b == 'C' || b == 'G' || b == 'T';
+        m |= (u64)ok << (c * 16 + j);
+      }
+    }
+    if (n - p0 < 64) m &= (1ULL << (n - p0)) - 1;
+  }
+  acgt[w] = m;
+}
+
+// bit p = the k characters from p are all A/C/G/T (so p + k <= n - 1: the sentinel is not).  Words w + 1 .. w + ceil(k/64) + 1 are
+// read; the caller pads the bitmap with that many zero words.
+__global__ void k_valid_bits(const u64* acgt, u64 nw_data, u32 k, u64* valid) {
+  const u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nw_data) return;
+  // first non-A/C/G/T position at or after 64 (w + 1), or far enough that no bit of this word cares
+  u64 nz = (w + 1) * 64 + k + 64;
+  const u32 look = (k + 63) / 64 + 1;
+  for (u32 j = 1; j <= look; ++j) {
+    const u64 z = ~acgt[w + j];
+    if (z) {
+      nz = (w + j) * 64 + (u64)__ffsll((long long)z) - 1;
+      break;
+    }
+  }
+  const u64 z0 = ~acgt[w];
+  u64 v = 0;
+  for (int b = 63; b >= 0; --b) {
+    const u64 p = w * 64 + (u64)b;
+    if ((z0 >> b) & 1ULL) nz = p;
+    v |= (u64)(nz - p >= k) << b;
+  }
+  valid[w] = v;
+}
+
+DG_DEV bool kmer_equal(const u8* t, u64 a, u64 b, u32 k) {
+  for (u32 j = 0; j < k; j += 8) {
+    u64 x = text8(t, a + j) ^ text8(t, b + j);
+    if (k - j < 8) x &= (1ULL << (8 * (k - j))) - 1;
+    if (x) return false;
+  }
+  return true;
+}
+
+// per rank i: bd bit i = a group of equal k-mers starts at rank i (every rank whose suffix has no valid k-mer is a group of its own),
+// hd bit i = that, and the k-mer at SA[i] is valid.  Launched with 256 threads per block: a wavefront's 64 ranks are one word.
+__global__ void __launch_bounds__(256) k_fwd_boundaries(FmView f, const u64* valid, u32 k, u64* bd, u64* hd) {
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = i < f.n;
+  bool boundary = true, head = false;
+  if (in) {
+    const u64 p = f.sa[i];
+    const bool vi = bit_at(valid, p);
+    if (vi && i > 0) {
+      const u64 q = f.sa[i - 1];
+      if (bit_at(valid, q)) boundary = !kmer_equal(f.text, q, p, k);
+    }
+    head = vi && boundary;
+  }
+  const u64 mb = __ballot(boundary), mh = __ballot(head);
+  if ((threadIdx.x & 63) == 0 && i < f.n) {
+    bd[i >> 6] = mb;
+    hd[i >> 6] = mh;
+  }
+}
+
+struct StartKey {  // rank i -> i where a group starts, else 0 (max-scan: the group's first rank)
+  const u64* bd;
+  __device__ __host__ u32 operator()(u32 i) const { return bit_at(bd, i) ? i : 0u; }
+};
+struct EndKey {  // j -> rank i = n-1-j if i is the last rank of its group, else ~0 (min-scan over j: the group's last rank)
+  const u64* bd;
+  u64 n;
+  __device__ __host__ u32 operator()(u32 j) const {
+    const u64 i = n - 1 - j;
+    return (i + 1 == n || bit_at(bd, i + 1)) ? (u32)i : 0xFFFFFFFFu;
+  }
+};
+struct MaxU32 {
+  __device__ __host__ u32 operator()(u32 a, u32 b) const { return a > b ? a : b; }
+};
+struct MinU32 {
+  __device__ __host__ u32 operator()(u32 a, u32 b) const { return a < b ? a : b; }
+};
+
+// group heads: the forward count is the group's size; the reverse count one backward search of revcomp(w).  Reading revcomp(w) from
+// its last character to its first is reading w from its first character to its last, complemented.  The head's slot of `start`
+// (which holds the head's own rank) receives the saturated total.
+__global__ void __launch_bounds__(256) k_heads(FmView f, u32 k, int forward_only, const u64* hd, u32* start, const u32* end_rev,
+                                              unsigned long long* steps) {
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  u32 n_ext = 0;
+  if (i < f.n && bit_at(hd, i)) {
+    const u64 fw = (u64)end_rev[f.n - 1 - i] - i + 1;
+    u64 rv = 0;
+    if (!forward_only) {
+      const u64 p = f.sa[i];
+      u32 lo = 0, hi = (u32)f.n, t = 0;
+      u64 chunk = 0;
+      if (f.K && k >= f.K) {
+        u64 code = 0;
+        for (; t < f.K; ++t) {
+          if ((t & 7) == 0) chunk = text8(f.text, p + t);
+          code |= (u64)(3u - acgt_code((u32)(chunk >> (8 * (t & 7))) & 255u)) << (2 * t);
+        }
+        const KtabEntry e = ktab_entry(f, code);
+        lo = e.lo;
+        hi = e.hi;
+      }
+      if (t < k && lo < hi) chunk = text8(f.text, p + (t & ~7u));
+      for (; t < k && lo < hi; ++t, ++n_ext) {
+        if ((t & 7) == 0) chunk = text8(f.text, p + t);
+        bs_extend_code_narrow(f, lo, hi, 3u - acgt_code((u32)(chunk >> (8 * (t & 7))) & 255u));
+      }
+      rv = lo < hi ? hi - lo : 0;
+    }
+    const u64 tot = fw + rv;
+    start[i] = tot > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)tot;
+  }
+  wave_add(steps, n_ext);  // (every lane of the wavefront is here)
+}
+
+// out[SA[i]] = the total of i's group (heads hold it in their own slot; members hold their head's rank), 0 for invalid ranks
+__global__ void k_scatter(FmView f, const u64* hd, const u32* start, u32 max_count, u32* out) {
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= f.n) return;
+  const u32 s = start[i];
+  u32 v = 0;
+  if (bit_at(hd, i)) v = s;
+  else if (s != (u32)i) v = start[s];
+  if (max_count && v > max_count) v = max_count;
+  out[f.sa[i]] = v;
+}
+
+// run boundaries of [a, b) inside the requested range [lo, hi): a run is a maximal stretch of equal non-zero values
+__global__ void k_run_flags(const u32* out, u64 lo, u64 hi, u64 a, u64 len, u8* fs, u8* fe) {
+  const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= len) return;
+  const u64 p = a + t;
+  const u32 v = out[p];
+  fs[t] = v && (p == lo || out[p - 1] != v);
+  fe[t] = v && (p + 1 == hi || out[p + 1] != v);
+}
+__global__ void k_run_values(const u32* out, u64 a, const u32* starts, const unsigned long long* cnt, u32* val) {
+  const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= cnt[0]) return;
+  val[t] = out[a + starts[t]];
+}
+
+static bool any_lane_busy(dg_index* ix) {  // as hunt.hip's
+  if (ix->busy.load()) return true;
+  std::lock_guard<std::mutex> lk(ix->lanes_mu);
+  for (dg_index* l : ix->lanes)
+    if (l && l->busy.load()) return true;
+  return false;
+}
+
+static int map_impl(dg_index* ix, const dg_map_params* prm, dg_map* m) {
+  const FmView& f = ix->view;
+  const u64 n = f.n;
+  const u32 k = prm->k;
+  hipStream_t st = ix->stream;
+  const u64 nw_data = (n + 63) / 64, nw = nw_data + (k + 63) / 64 + 4;
+  const size_t bm_bytes = nw * 8;
+  // scan scratch sizes first: everything is allocated before the first kernel runs
+  rocprim::counting_iterator<u32> cnt0(0);
+  auto sk = rocprim::make_transform_iterator(cnt0, StartKey{nullptr});
+  auto ek = rocprim::make_transform_iterator(cnt0, EndKey{nullptr, n});
+  size_t scan1 = 0, scan2 = 0;
+  DG_HIP(rocprim::inclusive_scan(nullptr, scan1, sk, (u32*)nullptr, (size_t)n, MaxU32(), st));
+  DG_HIP(rocprim::inclusive_scan(nullptr, scan2, ek, (u32*)nullptr, (size_t)n, MinU32(), st));
+  const size_t scan_bytes = std::max(scan1, scan2) + 256;
+  const u64 need = n * 4 + 256 + n * 4 + 256 + 3 * bm_bytes + scan_bytes + 64;
+  size_t free_b = 0, total_b = 0;
+  DG_HIP(hipMemGetInfo(&free_b, &total_b));
+  if ((u64)free_b < need + (64ULL << 20))
+    return fail(DG_ENOMEM, "dg_mappability: needs %llu MB of device memory, %llu MB free", (unsigned long long)(need >> 20),
+                (unsigned long long)(free_b >> 20));
+  struct Bufs {
+    hipStream_t st;
+    void *start = nullptr, *bm = nullptr, *scan = nullptr, *steps = nullptr;
+    ~Bufs() {
+      (void)hipStreamSynchronize(st);
+      if (start) big_free(start, st);
+      if (bm) big_free(bm, st);
+      if (scan) (void)hipFree(scan);
+      if (steps) (void)hipFree(steps);
+      (void)hipStreamSynchronize(st);
+    }
+  } b{st};
+  DG_HIP(big_alloc((void**)&m->out, n * 4 + 256, st));
+  DG_HIP(big_alloc(&b.start, n * 4 + 256, st));
+  DG_HIP(big_alloc(&b.bm, 3 * bm_bytes, st));
+  DG_HIP(hipMalloc(&b.scan, scan_bytes));
+  DG_HIP(hipMalloc(&b.steps, 8));
+  u64* acgt = (u64*)b.bm;  // becomes the boundary bitmap once the valid bitmap is made
+  u64* valid = acgt + nw;
+  u64* hd = valid + nw;
+  u64* bd = acgt;
+  u32* start = (u32*)b.start;
+  u32* end_rev = m->out;
+  hipEvent_t ev[5];
+  for (auto& e : ev) DG_HIP(hipEventCreate(&e));
+  struct Evs {
+    hipEvent_t* e;
+    ~Evs() {
+      for (int j = 0; j < 5; ++j) (void)hipEventDestroy(e[j]);
+    }
+  } evs{ev};
+  const u32 TB = 256;
+  DG_HIP(hipMemsetAsync(b.steps, 0, 8, st));
+  DG_HIP(hipEventRecord(ev[0], st));
+  hipLaunchKernelGGL(k_acgt_bits, dim3(ceil_div(nw, TB)), dim3(TB), 0, st, f.text, n, acgt, nw);
+  DG_HIP(hipMemsetAsync(valid + nw_data, 0, (nw - nw_data) * 8, st));
+  hipLaunchKernelGGL(k_valid_bits, dim3(ceil_div(nw_data, TB)), dim3(TB), 0, st, (const u64*)acgt, nw_data, k, valid);
+  DG_HIP(hipEventRecord(ev[1], st));
+  hipLaunchKernelGGL(k_fwd_boundaries, dim3(ceil_div(n, TB)), dim3(TB), 0, st, f, (const u64*)valid, k, bd, hd);
+  DG_HIP(rocprim::inclusive_scan(b.scan, scan1, rocprim::make_transform_iterator(cnt0, StartKey{bd}), start, (size_t)n, MaxU32(), st));
+  DG_HIP(rocprim::inclusive_scan(b.scan, scan2, rocprim::make_transform_iterator(cnt0, EndKey{bd, n}), end_rev, (size_t)n, MinU32(), st));
+  DG_HIP(hipEventRecord(ev[2], st));
+  hipLaunchKernelGGL(k_heads, dim3(ceil_div(n, TB)), dim3(TB), 0, st, f, k, prm->forward_only, (const u64*)hd, start, (const u32*)end_rev,
+                     (unsigned long long*)b.steps);
+  DG_HIP(hipEventRecord(ev[3], st));
+  hipLaunchKernelGGL(k_scatter, dim3(ceil_div(n, TB)), dim3(TB), 0, st, f, (const u64*)hd, (const u32*)start, prm->max_count, m->out);
+  DG_HIP(hipEventRecord(ev[4], st));
+  DG_HIP(hipMemcpyAsync(&m->st.rev_steps, b.steps, 8, hipMemcpyDeviceToHost, st));
+  DG_HIP(hipStreamSynchronize(st));
+  DG_HIP(hipGetLastError());
+  float ms[4] = {0, 0, 0, 0};
+  for (int j = 0; j < 4; ++j) DG_HIP(hipEventElapsedTime(&ms[j], ev[j], ev[j + 1]));
+  m->st.ms_valid = ms[0];
+  m->st.ms_forward = ms[1];
+  m->st.ms_reverse = ms[2];
+  m->st.ms_scatter = ms[3];
+  m->st.ms_total = ms[0] + ms[1] + ms[2] + ms[3];
+  m->st.transient_bytes = n * 4 + 256 + 3 * bm_bytes + scan_bytes;
+  return DG_OK;
+}
+
+}  // namespace dg
+
+using namespace dg;
+
+extern "C" {
+
+int dg_mappability(dg_index* ix, const dg_map_params* p, dg_map** out) {
+  if (out) *out = nullptr;
+  if (!ix || !p || !out) return fail(DG_EINVAL, "dg_mappability: null argument");
+  if (p->flags) return fail(DG_EINVAL, "dg_mappability: flags must be 0");
+  if (p->k < 10 || p->k > 1000) return fail(DG_ELIMIT, "dg_mappability: k = %u outside 10..1000", p->k);
+  if (ix->view.n < 2 || ix->view.n > 0xFFFFFFFFull) return fail(DG_ELIMIT, "dg_mappability: index of %llu suffixes", (unsigned long long)ix->view.n);
+  if (any_lane_busy(ix)) return fail(DG_EINVAL, "dg_mappability: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)");
+  DG_HIP(hipSetDevice(ix->device));
+  dg_map* m = new dg_map;
+  m->device = ix->device;
+  m->n = ix->view.n;
+  m->st.n = ix->view.n;
+  m->st.k = p->k;
+  if (hipStreamCreate(&m->stream) != hipSuccess) {
+    delete m;
+    return fail(DG_EHIP, "dg_mappability: cannot create a stream");
+  }
+  const int rc = map_impl(ix, p, m);
+  if (rc != DG_OK) {
+    delete m;
+    return rc;
+  }
+  *out = m;
+  return DG_OK;
+}
+
+int dg_map_values(dg_map* m, uint64_t lo, uint64_t hi, uint32_t* out) {
+  if (!m || (!out && hi > lo)) return fail(DG_EINVAL, "dg_map_values: null argument");
+  if (lo > hi || hi > m->n - 1) return fail(DG_EINVAL, "dg_map_values: range [%llu, %llu) outside [0, %llu)", (unsigned long long)lo,
+                                            (unsigned long long)hi, (unsigned long long)(m->n - 1));
+  if (hi == lo) return DG_OK;
+  DG_HIP(hipSetDevice(m->device));
+  DG_HIP(hipMemcpyAsync(out, m->out + lo, (hi - lo) * 4, hipMemcpyDeviceToHost, m->stream));
+  DG_HIP(hipStreamSynchronize(m->stream));
+  return DG_OK;
+}
+
+int dg_map_runs(dg_map* m, uint64_t lo, uint64_t hi, uint64_t* nruns, uint64_t** start, uint32_t** len, uint32_t** value) {
+  if (!m || !nruns || !start || !len || !value) return fail(DG_EINVAL, "dg_map_runs: null argument");
+  *nruns = 0;
+  *start = nullptr;
+  *len = nullptr;
+  *value = nullptr;
+  if (lo > hi || hi > m->n - 1) return fail(DG_EINVAL, "dg_map_runs: range [%llu, %llu) outside [0, %llu)", (unsigned long long)lo,
+                                            (unsigned long long)hi, (unsigned long long)(m->n - 1));
+  DG_HIP(hipSetDevice(m->device));
+  // the range goes through in chunks of positions; a run that crosses a chunk edge has its start in one chunk and its end in a later
+  // one, and since starts and ends alternate along the range the two lists pair up in order
+  u64 chunk = 1ULL << 24;
+  if (const char* e = exp_env("DICEY_MAP_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
+  const u64 cmax = std::min<u64>(chunk, hi - lo);
+  hipStream_t st = m->stream;
+  rocprim::counting_iterator<u32> cnt0(0);
+  size_t sel_bytes = 0;
+  DG_HIP(rocprim::select(nullptr, sel_bytes, cnt0, (const u8*)nullptr, (u32*)nullptr, (unsigned long long*)nullptr, (size_t)std::max<u64>(cmax, 1), st));
+  DG_TRY(m->run_flags.reserve(2 * cmax + 512 + sel_bytes));
+  DG_TRY(m->run_pos.reserve(8 * cmax + 64));
+  DG_TRY(m->run_val.reserve(4 * cmax + 64));
+  DG_TRY(m->run_cnt.reserve(64));
+  u8* fs = m->run_flags.as<u8>();
+  u8* fe = fs + cmax;
+  void* sel_tmp = (void*)(((uintptr_t)(fe + cmax) + 255) & ~(uintptr_t)255);
+  u32* ps = m->run_pos.as<u32>();
+  u32* pe = ps + cmax;
+  u32* pv = m->run_val.as<u32>();
+  unsigned long long* dc = m->run_cnt.as<unsigned long long>();
+  std::vector<u64> S, E;
+  std::vector<u32> V, hs, he;
+  for (u64 a = lo; a < hi; a += chunk) {
+    const u64 l = std::min<u64>(chunk, hi - a);
+    hipLaunchKernelGGL(k_run_flags, dim3(ceil_div(l, 256)), dim3(256), 0, st, (const u32*)m->out, lo, hi, a, l, fs, fe);
+    size_t b1 = sel_bytes;
+    DG_HIP(rocprim::select(sel_tmp, b1, cnt0, (const u8*)fs, ps, dc, (size_t)l, st));
+    DG_HIP(rocprim::select(sel_tmp, b1, cnt0, (const u8*)fe, pe, dc + 1, (size_t)l, st));
+    hipLaunchKernelGGL(k_run_values, dim3(ceil_div(l, 256)), dim3(256), 0, st, (const u32*)m->out, a, (const u32*)ps, (const unsigned long long*)dc, pv);
+    unsigned long long hc[2] = {0, 0};
+    DG_HIP(hipMemcpyAsync(hc, dc, 16, hipMemcpyDeviceToHost, st));
+    DG_HIP(hipStreamSynchronize(st));
+    hs.resize(hc[0]);
+    he.resize(hc[1]);
+    const size_t v0 = V.size();
+    V.resize(v0 + hc[0]);
+    if (hc[0]) {
+      DG_HIP(hipMemcpyAsync(hs.data(), ps, hc[0] * 4, hipMemcpyDeviceToHost, st));
+      DG_HIP(hipMemcpyAsync(V.data() + v0, pv, hc[0] * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (hc[1]) DG_HIP(hipMemcpyAsync(he.data(), pe, hc[1] * 4, hipMemcpyDeviceToHost, st));
+    DG_HIP(hipStreamSynchronize(st));
+    DG_HIP(hipGetLastError());
+    for (u32 x : hs) S.push_back(a + x);
+    for (u32 x : he) E.push_back(a + x);
+  }
+  if (S.size() != E.size() || S.size() != V.size())
+    return fail(DG_EHIP, "dg_map_runs: %zu run starts but %zu ends", S.size(), E.size());
+  const u64 nr = S.size();
+  uint64_t* s = (uint64_t*)std::malloc(nr * 8 + 8);
+  uint32_t* ln = (uint32_t*)std::malloc(nr * 4 + 4);
+  uint32_t* vv = (uint32_t*)std::malloc(nr * 4 + 4);
+  if (!s || !ln || !vv) {
+    std::free(s);
+    std::free(ln);
+    std::free(vv);
+    return fail(DG_ENOMEM, "dg_map_runs: %llu runs do not fit in host memory", (unsigned long long)nr);
+  }
+  for (u64 j = 0; j < nr; ++j) {
+    s[j] = S[j];
+    ln[j] = (uint32_t)(E[j] - S[j] + 1);
+    vv[j] = V[j];
+  }
+  *nruns = nr;
+  *start = s;
+  *len = ln;
+  *value = vv;
+  return DG_OK;
+}
+
+const void* dg_map_device_values(const dg_map* m) { return m ? m->out : nullptr; }
+
+int dg_map_stats(const dg_map* m, dg_map_stats_t* out) {
+  if (!m || !out) return fail(DG_EINVAL, "dg_map_stats: null argument");
+  *out = m->st;
+  return DG_OK;
+}
+
+void dg_map_free(dg_map* m) { delete m; }
+
+}  // extern "C"

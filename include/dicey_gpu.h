@@ -38,7 +38,8 @@ extern "C" {
  *    result buffers come from a pinned pool, dg_hunt_submit / dg_hunt_wait
  * 5: dg_hunt_params grows by max_query_len and flags; DG_HUNT_COMPACT: 8 + 4 d bytes per hit and 8 bytes per query cross PCIe / xGMI
  *    (dg_chit_unpack, dg_hunt_expand, dg_normalize_query turn them back); dg_hunt_submit keeps up to three batches in flight on ONE handle
- * 6: dg_hunt_result grows by stream / d_block / d_block_bytes (the gather over RCCL lives in libdiceygather.so, include/dicey_gather.h) */
+ * 6: dg_hunt_result grows by stream / d_block / d_block_bytes (the gather over RCCL lives in libdiceygather.so, include/dicey_gather.h)
+ * 7 (additive exports, same version): dg_mappability, dg_map_values, dg_map_runs, dg_map_device_values, dg_map_stats, dg_map_free */
 #define DG_ABI_VERSION 7
 
 enum {
@@ -424,6 +425,46 @@ void dg_search_result_free(dg_search_result* r);
  * count or invariant is off — what a maintainer needs when the first genuine `dicey index` file does not load. */
 #define DG_FM9_CHECK_DEEP 1u
 int dg_fm9_check(const char* fm9_path, uint32_t flags, char* report, size_t report_cap);
+
+/* ABI 7, additive (the version stays 7: nothing that existed changed).  `dicey mappability`: exact-match k-mer uniqueness of every text
+ * position, on the resident index.  For T = SEQ1 '\n' SEQ2 '\n' ... (the text `dicey index` wrote, sentinel at n-1), k in 10..1000
+ * (else DG_ELIMIT) and a position p < n-1: value(p) = 0 when p + k > n-1 or T[p, p+k) holds a byte other than A/C/G/T (N, IUPAC
+ * letters, the '\n' between sequences: a k-mer never crosses a sequence); otherwise count(w) + count(revcomp(w)) for w = T[p, p+k),
+ * count = sdsl::count (overlapping occurrences included) — the both-strand total of `padlock` (hits[0] + hits[1]).  A reverse-complement
+ * palindrome (w == revcomp(w), even k only) therefore counts TWICE per occurrence.  forward_only: count(w) alone.  Every valid position
+ * has value >= 1; values saturate at 0xFFFFFFFF; max_count = C > 0 writes min(value, C) (C = 2: a unique / non-unique track).
+ * This is NOT upstream dicey's chop + aligner + mappability pipeline.  The computation runs on the handle's stream and needs about
+ * 8n + 3n/8 bytes of free HBM beside the index (DG_ENOMEM before any kernel otherwise); DG_EINVAL while a dg_hunt_submit batch is in
+ * flight on the handle.  The map keeps u32[n-1] values in HBM and a stream of its own; free it before closing the index. */
+typedef struct {
+  uint32_t k;           /* k-mer length, 10..1000 */
+  int32_t forward_only; /* count(w) only */
+  uint32_t max_count;   /* 0 = exact values, else min(value, max_count) */
+  uint32_t flags;       /* 0 */
+} dg_map_params;
+typedef struct dg_map dg_map;
+typedef struct {
+  uint64_t n;               /* the index's n: values cover positions [0, n-1) */
+  uint32_t k, reserved;
+  double ms_valid;          /* device time: valid-position bitmap */
+  double ms_forward;        /* group boundaries in suffix-array order + the two scans (forward counts) */
+  double ms_reverse;        /* backward search of revcomp(w) per group of equal k-mers (0-ish with forward_only) */
+  double ms_scatter;        /* values to text positions */
+  double ms_total;
+  uint64_t rev_steps;       /* backward-search steps taken behind the K-mer table (measurement) */
+  uint64_t transient_bytes; /* HBM held during the computation beside the result */
+} dg_map_stats_t;
+int dg_mappability(dg_index* ix, const dg_map_params* p, dg_map** out);
+/* values of positions [lo, hi) (hi <= n-1) to the host */
+int dg_map_values(dg_map* m, uint64_t lo, uint64_t hi, uint32_t* out);
+/* maximal runs of equal non-zero values inside [lo, hi), in position order: run r covers start[r] .. start[r] + len[r] - 1 with
+ * value[r].  A run is cut at lo and hi, never elsewhere.  The three arrays are library buffers (release each with dg_buffer_free);
+ * only the runs cross PCIe. */
+int dg_map_runs(dg_map* m, uint64_t lo, uint64_t hi, uint64_t* nruns, uint64_t** start, uint32_t** len, uint32_t** value);
+/* u32[n-1] on the index's device, valid until dg_map_free */
+const void* dg_map_device_values(const dg_map* m);
+int dg_map_stats(const dg_map* m, dg_map_stats_t* out);
+void dg_map_free(dg_map* m); /* NULL: no-op */
 
 const char* dg_last_error(void);
 int dg_abi_version(void);

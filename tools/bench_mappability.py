@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""Whole-genome timing of dg_mappability (include/dicey_gpu.h) and of `dicey mappability -o` — not the headline bench.  The genome
+is bench.py's synthetic GRCh38-size text (--genome iid | repeats), generated on the device from a seed and indexed with
+dg_index_build_device, or an existing index (--fm9).  Per k: device phase times from HIP events (dg_map_stats), both strands and
+forward only.  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
+Prints one JSON line."""
+import argparse, ctypes as C, json, os, subprocess, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+import bench, dicey_amd
+from dicey_amd import _capi
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--genome-size", type=float, default=3.1e9)
+ap.add_argument("--genome", choices=["iid", "repeats"], default="iid")
+ap.add_argument("--fm9", default="", help="reuse this index (its .lens.json beside it holds the sequence lengths)")
+ap.add_argument("--ks", default="24,36,50,100,150")
+ap.add_argument("--cli-k", type=int, default=100)
+ap.add_argument("--workdir", default="/dev/shm")
+a = ap.parse_args()
+dev = torch.device("cuda", 0)
+L = _capi.load()
+out = {"tool": "bench_mappability", "genome": a.genome, "genome_size": a.genome_size}
+fm9 = a.fm9 or os.path.join(a.workdir, "dicey_map_bench_%s.fm9" % a.genome)
+if not a.fm9:
+    t0 = time.time()
+    text, lens = bench.synth_genome(int(a.genome_size), 24, seed=1, device=dev, repeats=a.genome == "repeats")
+    _capi.check(L, L.dg_index_build_device(C.c_void_p(text.data_ptr()), text.numel(), 0, fm9.encode()))
+    json.dump([int(x) for x in lens], open(fm9 + ".lens.json", "w"))
+    out["build_s"] = round(time.time() - t0, 2)
+    del text
+    torch.cuda.empty_cache()
+lens = json.load(open(fm9 + ".lens.json"))
+t0 = time.time()
+ix = dicey_amd.FmIndex(fm9, compact=True, pre5=False)
+out["open_s"] = round(time.time() - t0, 2)
+n = ix.size()
+out["n"] = n
+runs = []
+for k in [int(x) for x in a.ks.split(",")]:
+    for fo in (False, True):
+        prm = _capi.MapParams(k, 1 if fo else 0, 0, 0)
+        m = C.c_void_p()
+        t0 = time.time()
+        _capi.check(L, L.dg_mappability(ix.handle, C.byref(prm), C.byref(m)))
+        wall = time.time() - t0
+        st = _capi.MapStats()
+        _capi.check(L, L.dg_map_stats(m, C.byref(st)))
+        L.dg_map_free(m)
+        runs.append({"k": k, "forward_only": fo, "ms_total": round(st.ms_total, 1), "ms_valid": round(st.ms_valid, 1),
+                     "ms_forward": round(st.ms_forward, 1), "ms_reverse": round(st.ms_reverse, 1), "ms_scatter": round(st.ms_scatter, 1),
+                     "forward_share": round((st.ms_valid + st.ms_forward + st.ms_scatter) / max(st.ms_total, 1e-9), 3),
+                     "rev_steps": st.rev_steps, "wall_s": round(wall, 2), "transient_gb": round(st.transient_bytes / 1e9, 2)})
+        print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+out["runs"] = runs
+ix.close()
+# the CLI end to end: open + map + runs + format + gzip
+stem = os.path.join(a.workdir, "dicey_map_bench_cli_%s" % a.genome)
+with open(stem + ".fa", "w") as f:
+    f.write(">chr1\nN\n")
+with open(stem + ".fa.fai", "w") as f:
+    for i, l in enumerate(lens):
+        f.write("chr%d\t%d\t0\t60\t61\n" % (i + 1, l))
+if os.path.lexists(stem + ".fm9"):
+    os.remove(stem + ".fm9")
+os.symlink(os.path.abspath(fm9), stem + ".fm9")
+gz = stem + ".bedgraph.gz"
+t0 = time.time()
+r = subprocess.run([os.path.join(ROOT, "dicey_amd", "dicey"), "mappability", "-g", stem + ".fa", "-k", str(a.cli_k), "-o", gz],
+                   capture_output=True, text=True)
+out["cli"] = {"k": a.cli_k, "rc": r.returncode, "wall_s": round(time.time() - t0, 2),
+              "gz_bytes": os.path.getsize(gz) if os.path.exists(gz) else 0, "stderr": r.stderr[-300:]}
+for p in (gz, stem + ".fm9", stem + ".fa", stem + ".fa.fai") + (() if a.fm9 else (fm9, fm9 + ".lens.json")):
+    if os.path.lexists(p):
+        os.remove(p)
+print(json.dumps(out))

@@ -5,7 +5,7 @@ set -e
 cd "$(dirname "$0")/../dicey_amd/csrc"
 N=$1; shift
 mkdir -p ../variants build_$N
-for f in index seam hunt search build thal_api padlock; do
+for f in index seam hunt search build thal_api padlock mappability; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -ffp-contract=off "$@" -c $f.hip -o build_$N/$f.o &
 done
 wait
