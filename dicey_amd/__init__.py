@@ -56,6 +56,8 @@ class HuntBatch:
     queries: List[QueryResult]
     counters: dict
     timings_ms: dict
+    # which kernels the batch's last attempt ran and how its capped queries were enumerated (dg_hunt_result fields of the same names)
+    path: dict = field(default_factory=dict)
 
 
 def _pack(items: Sequence[bytes]):
@@ -229,7 +231,8 @@ class FmIndex:
                "win_bytes": R.ctr_win_bytes, "tab_reads": R.ctr_tab_reads, "filter_probes": R.ctr_filter_probes, "nhits": R.nhits}
         tm = {"total": R.ms_total, "search": R.ms_search, "select": R.ms_select, "locate": R.ms_locate,
               "verify": R.ms_verify}
-        return HuntBatch(qs, ctr, tm)
+        path = {f: getattr(R, f) for f in ("flat_kernel_form", "verify_kernel_form", "cap_queries_device", "cap_queries_host", "cap_patterns")}
+        return HuntBatch(qs, ctr, tm, path)
 
     @staticmethod
     def _params(distance, hamming, forward_only, max_locations, max_neighborhood, compact, max_query_len):

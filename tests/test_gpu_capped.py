@@ -21,13 +21,29 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def ix(small_genome):
+def handles(small_genome):
+    """one handle per library, opened at first use: the product library for the device path, the development build for the host
+    path (DICEY_CAP_HOST — read per batch — is a test switch the product library ignores, experiments.hpp)"""
     import dicey_amd
     from conftest import exp_lib
-    # (the development build: DICEY_CAP_HOST — read per batch — is a test switch the product library ignores, experiments.hpp)
-    h = dicey_amd.FmIndex(small_genome["fm9"], device=0, _lib=exp_lib())
-    yield h
-    h.close()
+    hs = {}
+
+    def get(path):
+        if path not in hs:
+            hs[path] = dicey_amd.FmIndex(small_genome["fm9"], device=0, _lib=exp_lib() if path == "host" else None)
+        return hs[path]
+    yield get
+    for h in hs.values():
+        h.close()
+
+
+@pytest.fixture
+def ix(handles, cap_path):
+    from dicey_amd import _capi
+    h = handles(cap_path)
+    if cap_path == "device":
+        assert h._L is _capi.load()
+    return h
 
 
 @pytest.fixture(params=["device", "host"], autouse=True)

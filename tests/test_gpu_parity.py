@@ -455,6 +455,25 @@ def test_randomised_configurations_against_oracle():
     assert "failing configurations: 0" in r.stdout, r.stdout[-1500:]
 
 
+@pytest.mark.parametrize("seed,nconf,one_shot", [(2, 8, False), (1, 8, False), (9, 8, False), (5, 6, True)])
+def test_n_run_fuzzer_against_oracle(seed, nconf, one_shot):
+    """tools/fuzz_n.py (queries at N runs and sequence ends; found round 6's k_nkeep and ninth-edit hit losses): the seeds draw the
+    text's shortest N run 1 (no pruning), 2, 3 and 6; the last one with the open flags of `dicey hunt` (FUZZ_ONE_SHOT)"""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = dict(os.environ)
+    env.pop("FUZZ_ONE_SHOT", None)
+    if one_shot:
+        env["FUZZ_ONE_SHOT"] = "1"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_n.py"), str(seed), str(nconf)], capture_output=True, text=True,
+                       timeout=120, env=env)
+    assert r.returncode == 0, r.stderr[-1500:]
+    assert "failing configurations: 0" in r.stdout, r.stdout[-1500:]
+    assert "library refused" not in r.stdout, r.stdout[-1500:]  # distances 0-2, queries up to 31 nt: nothing here may be refused
+    assert "nmin %d " % {2: 1, 1: 2, 9: 3, 5: 6}[seed] in r.stdout, r.stdout[-500:]
+
+
 def test_device_entry_point_rechecks_a_cached_length_bound(gpu_small, small_genome):
     """dg_hunt_device skips reading the offsets back when buffer, count and byte total repeat; offsets rewritten in place
     with a longer query are caught on the device and the batch is redone."""
