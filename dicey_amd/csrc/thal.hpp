@@ -17,6 +17,11 @@
 #define DG_HD inline
 #endif
 
+// test builds count the openings whose candidate wins with S below the entropy cut-off (tests/host/thal_host.cpp); the product defines nothing
+#ifndef DG_THAL_CUTOFF_WIN
+#define DG_THAL_CUTOFF_WIN()
+#endif
+
 namespace dg {
 namespace thal {
 
@@ -386,6 +391,7 @@ DG_HD Result end1_tm(const Tables& T, const Env& env, const SeqT& a, int len1, c
             if (lS < kMinEntropyCutoff) {
               lS = kMinEntropy;
               lH = 0.0;
+              DG_THAL_CUTOFF_WIN();
             }
             if (fin(lH)) {
               curH = lH;

@@ -14,132 +14,11 @@
 
 #include "iupac.hpp"
 #include "thal_internal.hpp"
+#include "thal_tables.hpp"
 #include "thal_wave.hpp"
 
 namespace dg {
 namespace {
-
-// one value per line, possibly "inf" (thal.h:403-414)
-struct ValueFile {
-  std::ifstream f;
-  bool ok;
-  explicit ValueFile(const std::string& p) : f(p.c_str()), ok(f.good()) {}
-  bool line(std::string& s) { return (bool)std::getline(f, s); }
-  double next() {
-    std::string s;
-    if (!line(s)) {
-      ok = false;
-      return 0;
-    }
-    size_t k = 0;
-    while (k < s.size() && std::isspace((unsigned char)s[k])) ++k;
-    if (s.compare(k, 3, "inf") == 0) return thal::kInf;
-    return std::strtod(s.c_str() + k, nullptr);
-  }
-};
-static double field(const std::string& tok) { return tok == "inf" ? thal::kInf : std::strtod(tok.c_str(), nullptr); }
-
-static int load_tables(const std::string& dir, thal::Tables& t) {
-  using thal::fin;
-  using thal::kInf;
-  auto quad = [&](const char* sname, const char* hname, double S[5][5][5][5], double H[5][5][5][5], bool terminal) -> int {
-    ValueFile fs(dir + sname), fh(dir + hname);
-    if (!fs.ok || !fh.ok) return fail(DG_EIO, "cannot read %s%s / %s", dir.c_str(), sname, hname);
-    for (int i = 0; i < 5; ++i)
-      for (int ii = 0; ii < 5; ++ii)
-        for (int j = 0; j < 5; ++j)
-          for (int jj = 0; jj < 5; ++jj) {
-            if (!terminal) {  // getStack / getStackint2 (thal.h:497-555)
-              if (i == 4 || j == 4 || ii == 4 || jj == 4) {
-                S[i][ii][j][jj] = -1.0;
-                H[i][ii][j][jj] = kInf;
-                continue;
-              }
-            } else {  // getTstack / getTstack2 (thal.h:622-679)
-              if (i == 4 || j == 4) {
-                H[i][ii][j][jj] = kInf;
-                S[i][ii][j][jj] = -1.0;
-                continue;
-              }
-              if (ii == 4 || jj == 4) {
-                S[i][ii][j][jj] = 0.00000000001;
-                H[i][ii][j][jj] = 0.0;
-                continue;
-              }
-            }
-            S[i][ii][j][jj] = fs.next();
-            H[i][ii][j][jj] = fh.next();
-            if (!fin(S[i][ii][j][jj]) || !fin(H[i][ii][j][jj])) {
-              S[i][ii][j][jj] = -1.0;
-              H[i][ii][j][jj] = kInf;
-            }
-          }
-    if (!fs.ok || !fh.ok) return fail(DG_EFORMAT, "%s%s / %s are too short", dir.c_str(), sname, hname);
-    return DG_OK;
-  };
-  DG_TRY(quad("stack.ds", "stack.dh", t.stackS, t.stackH, false));
-  DG_TRY(quad("stackmm.ds", "stackmm.dh", t.stackmmS, t.stackmmH, false));
-  {  // getDangle (thal.h:558-604): 3' block then 5' block in the same files
-    ValueFile fs(dir + "dangle.ds"), fh(dir + "dangle.dh");
-    if (!fs.ok || !fh.ok) return fail(DG_EIO, "cannot read %sdangle.ds/.dh", dir.c_str());
-    for (int i = 0; i < 5; ++i)
-      for (int j = 0; j < 5; ++j)
-        for (int k = 0; k < 5; ++k) {
-          if (i == 4 || j == 4 || k == 4) {
-            t.dangle3S[i][k][j] = -1.0;
-            t.dangle3H[i][k][j] = kInf;
-          } else {
-            t.dangle3S[i][k][j] = fs.next();
-            t.dangle3H[i][k][j] = fh.next();
-            if (!fin(t.dangle3S[i][k][j]) || !fin(t.dangle3H[i][k][j])) {
-              t.dangle3S[i][k][j] = -1.0;
-              t.dangle3H[i][k][j] = kInf;
-            }
-          }
-        }
-    for (int i = 0; i < 5; ++i)
-      for (int j = 0; j < 5; ++j)
-        for (int k = 0; k < 5; ++k) {
-          if (i == 4 || j == 4 || k == 4) {
-            t.dangle5S[i][j][k] = -1.0;
-            t.dangle5H[i][j][k] = kInf;
-          } else {
-            t.dangle5S[i][j][k] = fs.next();
-            t.dangle5H[i][j][k] = fh.next();
-            if (!fin(t.dangle5S[i][j][k]) || !fin(t.dangle5H[i][j][k])) {
-              t.dangle5S[i][j][k] = -1.0;
-              t.dangle5H[i][j][k] = kInf;
-            }
-          }
-        }
-    if (!fs.ok || !fh.ok) return fail(DG_EFORMAT, "%sdangle.ds/.dh are too short", dir.c_str());
-  }
-  {  // getLoop (thal.h:606-620): "<size> <interior> <bulge> <hairpin>" per line, 30 lines
-    ValueFile fs(dir + "loops.ds"), fh(dir + "loops.dh");
-    if (!fs.ok || !fh.ok) return fail(DG_EIO, "cannot read %sloops.ds/.dh", dir.c_str());
-    for (int k = 0; k < 30; ++k) {
-      std::string ls, lh, a, b, c, d;
-      if (!fs.line(ls) || !fh.line(lh)) return fail(DG_EFORMAT, "%sloops.ds/.dh are too short", dir.c_str());
-      std::istringstream ss(ls), sh(lh);
-      ss >> a >> b >> c >> d;
-      t.interiorS[k] = field(b);
-      t.bulgeS[k] = field(c);
-      sh >> a >> b >> c >> d;
-      t.interiorH[k] = field(b);
-      t.bulgeH[k] = field(c);
-    }
-  }
-  DG_TRY(quad("tstack_tm_inf.ds", "tstack.dh", t.tstackS, t.tstackH, true));
-  DG_TRY(quad("tstack2.ds", "tstack2.dh", t.tstack2S, t.tstack2H, true));
-  for (int i = 0; i < 5; ++i)
-    for (int j = 0; j < 5; ++j) {  // tableStartATS / tableStartATH (thal.h:767-783), AT_S = 6.9, AT_H = 2200
-      t.atpS[i][j] = 0.00000000001;
-      t.atpH[i][j] = 0.0;
-    }
-  t.atpS[0][3] = t.atpS[3][0] = 6.9;
-  t.atpH[0][3] = t.atpH[3][0] = 2200.0;
-  return DG_OK;
-}
 
 struct PairDesc {
   u64 a_off, b_off, dp_off;  // framed codes of oligo 1 / reversed oligo 2, DP planes
@@ -255,21 +134,6 @@ __global__ void __launch_bounds__(1024) k_thal_self_wave(const thal::Tables* T, 
   }
 }
 
-static u8 code_of(char c) {
-  c = (char)std::toupper((unsigned char)c);
-  return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4;  // str2int, thal.h:260-275
-}
-// symmetry_thermo (thal.h:1976-2010): even length and self-complementary
-static bool self_complementary(const u8* s, size_t n) {
-  if (n % 2) return false;
-  for (size_t i = 0; i < n / 2; ++i) {
-    char a = (char)std::toupper(s[i]), b = (char)std::toupper(s[n - 1 - i]);
-    if ((a == 'A' && b != 'T') || (a == 'T' && b != 'A') || (b == 'A' && a != 'T') || (b == 'T' && a != 'A')) return false;
-    if ((a == 'C' && b != 'G') || (a == 'G' && b != 'C') || (b == 'C' && a != 'G') || (b == 'G' && a != 'C')) return false;
-  }
-  return true;
-}
-
 }  // namespace
 }  // namespace dg
 
@@ -287,17 +151,13 @@ int dg_thal_open(const char* config_dir, double mv, double dv, double dntp, doub
   if (!dir.empty() && dir.back() != '/') dir.push_back('/');
   dg_thal* th = new dg_thal;
   th->device = device;
-  int rc = load_tables(dir, th->host_tables);
-  if (rc != DG_OK) {
+  std::string err;
+  int rc = thal::load_tables(dir, th->host_tables, err);
+  if (rc != thal::kLoadOk) {
     delete th;
-    return rc;
+    return fail(rc == thal::kLoadIo ? DG_EIO : DG_EFORMAT, "%s", err.c_str());
   }
-  // saltCorrectS (thal.h:354-359) and the two RC values (thal.h:2504-2508)
-  double dn = dntp;
-  if (dv <= 0) dn = dv;
-  th->env.salt_correction = 0.368 * ((log((mv + 120 * (sqrt(fmax(0.0, dv - dn)))) / 1000)));
-  th->env.rc_sym = 1.9872 * log(dna_conc / 1000000000.0);
-  th->env.rc_asym = 1.9872 * log(dna_conc / 4000000000.0);
+  th->env = thal::make_env(mv, dv, dntp, dna_conc);  // thal_tables.hpp: the salt correction and the two RC values
   auto body = [&]() -> int {
     DG_HIP(hipSetDevice(device));
     DG_HIP(hipStreamCreate(&th->stream));
@@ -335,7 +195,7 @@ int dg_thal_batch(dg_thal* th, const uint8_t* seqs, const uint64_t* off, size_t 
   static u8 lut[256];
   static bool lut_ready = false;
   if (!lut_ready) {
-    for (int c = 0; c < 256; ++c) lut[c] = code_of((char)c);
+    for (int c = 0; c < 256; ++c) lut[c] = thal::code_of((char)c);
     lut_ready = true;
   }
   for (size_t k = 0; k < npairs; ++k) {
@@ -347,7 +207,7 @@ int dg_thal_batch(dg_thal* th, const uint8_t* seqs, const uint64_t* off, size_t 
     ncode += l1 + 2;
     pd[k].b_off = ncode;
     ncode += l2 + 2;
-    pd[k].symmetric = self_complementary(seqs + off[2 * k], l1) && self_complementary(seqs + off[2 * k + 1], l2);
+    pd[k].symmetric = thal::self_complementary(seqs + off[2 * k], l1) && thal::self_complementary(seqs + off[2 * k + 1], l2);
     pd[k].pad = (!no_wave && l1 >= 1 && l2 >= 1 && l1 <= kWaveLenCap && l2 <= kWaveLenCap) ? 1 : 0;  // wave kernel takes it
     pd[k].dp_off = ndp;  // the sequential kernel's table; hand-backs of the wave kernel get theirs in the second pass
     const bool both_long = l1 > (u64)thal::kMaxAlign && l2 > (u64)thal::kMaxAlign;

@@ -109,11 +109,18 @@ def test_padlock_scan_arrays(scenario):
         # arm Tm equals thal(arm, revcomp) of the batch API wherever the GC filter passes; windows with N have GC -1
         ex = exons[0].decode()
         want = th.tm([(ex[q:q + 20], revcomp(ex[q:q + 20])) for q in range(0, 60)])
+        ref = None
+        if O.ref_libs() is not None:   # the reference's own thal() on the same windows
+            import thal_corpus as TC
+            import thal_expect as TE
+            ref = TE.ref_values([(ex[q:q + 20], revcomp(ex[q:q + 20])) for q in range(0, 60)], TC.ENVS["default"])
         for q in range(60):
             gc = (ex[q:q + 20].count("C") + ex[q:q + 20].count("G")) / 20
             assert R["arm_gc"][q] == gc
             if 0.4 <= gc <= 0.6:
                 assert R["arm_tm"][q] == want[q][0]
+                if ref is not None:
+                    assert ref[q][3] and TE.hexd(R["arm_tm"][q]) == ref[q][0]
             else:
                 assert R["arm_tm"][q] == -1e300
         o3 = int(off[3])
