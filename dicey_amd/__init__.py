@@ -147,18 +147,25 @@ class FmIndex:
         finally:
             self._L.dg_locations_free(lp)
 
-    def _map(self, k, forward_only, max_count):
-        prm = _capi.MapParams(k, 1 if forward_only else 0, max_count, 0)
+    def _map(self, k, forward_only, max_count, mismatches=0):
         m = C.c_void_p()
-        _capi.check(self._L, self._L.dg_mappability(self._h, C.byref(prm), C.byref(m)))
+        if mismatches == 0:
+            prm = _capi.MapParams(k, 1 if forward_only else 0, max_count, 0)
+            _capi.check(self._L, self._L.dg_mappability(self._h, C.byref(prm), C.byref(m)))
+        else:
+            prm = _capi.MapMmParams(k, mismatches, 1 if forward_only else 0, max_count, 0, 0)
+            _capi.check(self._L, self._L.dg_mappability_mm(self._h, C.byref(prm), C.byref(m)))
         return m
 
-    def mappability(self, k: int = 100, forward_only: bool = False, max_count: int = 0, stats: Optional[dict] = None):
-        """Exact-match k-mer uniqueness of every text position (include/dicey_gpu.h dg_mappability): numpy uint32 array of n-1
-        values, value[p] = count(w) + count(revcomp(w)) for the k-mer w at p (count(w) alone with forward_only), 0 where no
-        k-mer of A/C/G/T starts; min(value, max_count) when max_count > 0.  `stats`, when given, receives the phase times."""
+    def mappability(self, k: int = 100, forward_only: bool = False, max_count: int = 0, stats: Optional[dict] = None,
+                    mismatches: int = 0):
+        """k-mer uniqueness of every text position (include/dicey_gpu.h dg_mappability / dg_mappability_mm): numpy uint32 array of
+        n-1 values, value[p] = count(w) + count(revcomp(w)) for the k-mer w at p (count(w) alone with forward_only), 0 where no
+        k-mer of A/C/G/T starts; min(value, max_count) when max_count > 0.  With mismatches = e in 1..2 the counts are those of
+        the windows within Hamming distance e of w and of revcomp(w): (k,e)-mappability.  `stats`, when given, receives the phase
+        times and, for e > 0, the search counters (dg_map_mm_stats_t)."""
         import numpy as np
-        m = self._map(k, forward_only, max_count)
+        m = self._map(k, forward_only, max_count, mismatches)
         try:
             st = _capi.MapStats()
             _capi.check(self._L, self._L.dg_map_stats(m, C.byref(st)))
@@ -166,14 +173,19 @@ class FmIndex:
             _capi.check(self._L, self._L.dg_map_values(m, 0, st.n - 1, out.ctypes.data_as(C.POINTER(C.c_uint32))))
             if stats is not None:
                 stats.update({f: getattr(st, f) for f, _ in _capi.MapStats._fields_ if f != "reserved"})
+                if mismatches > 0:
+                    mm = _capi.MapMmStats()
+                    _capi.check(self._L, self._L.dg_map_mm_stats(m, C.byref(mm)))
+                    stats.update({f: getattr(mm, f) for f, _ in _capi.MapMmStats._fields_})
             return out
         finally:
             self._L.dg_map_free(m)
 
-    def mappability_runs(self, k: int = 100, forward_only: bool = False, max_count: int = 0, lo: int = 0, hi: Optional[int] = None):
+    def mappability_runs(self, k: int = 100, forward_only: bool = False, max_count: int = 0, lo: int = 0, hi: Optional[int] = None,
+                         mismatches: int = 0):
         """The same values as maximal runs of equal non-zero values inside text positions [lo, hi) (hi = n-1 when None): numpy
         arrays (start uint64, length uint32, value uint32); a run is cut at lo and hi."""
-        m = self._map(k, forward_only, max_count)
+        m = self._map(k, forward_only, max_count, mismatches)
         try:
             if hi is None:
                 st = _capi.MapStats()

@@ -91,6 +91,16 @@ class MapStats(C.Structure):
                 ("transient_bytes", C.c_uint64)]
 
 
+class MapMmParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("mismatches", C.c_uint32), ("forward_only", C.c_int32), ("max_count", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MapMmStats(C.Structure):
+    _fields_ = [("heads", C.c_uint64), ("steps", C.c_uint64), ("table_reads", C.c_uint64), ("verified_rows", C.c_uint64),
+                ("early_exits", C.c_uint64), ("launches", C.c_uint64), ("ms_search", C.c_double)]
+
+
 # every symbol include/dicey_gpu.h declares; tests/test_capi_symbols.py checks the list against the header
 class PadlockParams(C.Structure):
     _fields_ = [("armlen", C.c_uint32), ("distance", C.c_uint32), ("hamming", C.c_int32), ("tmdiff", C.c_uint32),
@@ -111,7 +121,8 @@ SYMBOLS = ["dg_index_open", "dg_index_close", "dg_index_stats", "dg_count", "dg_
            "dg_neighborhood_count", "dg_padlock_scan", "dg_padlock_result_free", "dg_index_share",
            "dg_neighbors", "dg_buffer_free", "dg_hit_rows", "dg_hunt_rows", "dg_hunt_submit", "dg_hunt_wait", "dg_hunt_device_submit",
            "dg_chit_unpack", "dg_normalize_query", "dg_hunt_expand", "dg_index_stream", "dg_fm9_check",
-           "dg_mappability", "dg_map_values", "dg_map_runs", "dg_map_device_values", "dg_map_stats", "dg_map_free"]
+           "dg_mappability", "dg_map_values", "dg_map_runs", "dg_map_device_values", "dg_map_stats", "dg_map_free",
+           "dg_mappability_mm", "dg_map_mm_stats"]
 
 _lib = None
 
@@ -185,6 +196,8 @@ def load(path=None):
     L.dg_map_device_values.restype = vp
     L.dg_map_stats.argtypes = [vp, C.POINTER(MapStats)]
     L.dg_map_free.argtypes = [vp]
+    L.dg_mappability_mm.argtypes = [vp, C.POINTER(MapMmParams), C.POINTER(vp)]
+    L.dg_map_mm_stats.argtypes = [vp, C.POINTER(MapMmStats)]
     L.dg_map_free.restype = None
     if path is None:
         _lib = L

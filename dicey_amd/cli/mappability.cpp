@@ -17,7 +17,8 @@ int mappability_main(int argc, char** argv);
 namespace {
 
 const OptSpec kMapOpts[] = {{"help", '?', false},  {"genome", 'g', true},  {"kmer", 'k', true},
-                            {"forward", 'f', false}, {"maxcount", 'c', true}, {"outfile", 'o', true}};
+                            {"forward", 'f', false}, {"maxcount", 'c', true}, {"outfile", 'o', true},
+                            {"mismatches", 'e', true}};
 
 void map_usage() {
   std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz" << std::endl;
@@ -25,6 +26,7 @@ void map_usage() {
                "  -? [ --help ]                      show help message\n"
                "  -g [ --genome ] arg                genome file (indexed with dicey index: <genome stem>.fm9)\n"
                "  -k [ --kmer ] arg (=100)           k-mer length (10..1000)\n"
+               "  -e [ --mismatches ] arg (=0)       count k-mers with up to this many mismatches (0..2)\n"
                "  -f [ --forward ]                   forward strand only\n"
                "  -c [ --maxcount ] arg (=0)         write min(value, maxcount); 0 = exact values\n"
                "  -o [ --outfile ] arg               gzipped output file (default: plain text on stdout)\n"
@@ -32,7 +34,9 @@ void map_usage() {
                "Output: bedGraph lines name, start, end, value (0-based, end exclusive) of maximal runs of equal values, where the value\n"
                "of a k-mer start position is the number of occurrences of that k-mer plus those of its reverse complement in the\n"
                "genome (forward only: the k-mer alone; a reverse-complement palindrome counts twice).  Positions whose k-mer holds a\n"
-               "character other than A/C/G/T or runs past the sequence end have no line.\n"
+               "character other than A/C/G/T or runs past the sequence end have no line.  With -e 1 or -e 2 the value counts the k-mers\n"
+               "of the genome within that many mismatches (substitutions) of the k-mer and of its reverse complement, the k-mer\n"
+               "itself included ((k,e)-mappability); k-mers with a character other than A/C/G/T are never counted.\n"
                "\n";
 }
 
@@ -83,7 +87,7 @@ int mappability_main(int argc, char** argv) {
   }
   std::string genome, outfile;
   bool help = false, have_genome = false, forward = false;
-  long long k = 100, maxcount = 0;
+  long long k = 100, maxcount = 0, mismatches = 0;
   for (auto& kv : p.kv) {
     if (kv.first == "help") help = true;
     else if (kv.first == "genome") { genome = kv.second; have_genome = true; }
@@ -91,12 +95,14 @@ int mappability_main(int argc, char** argv) {
     else if (kv.first == "forward") forward = true;
     else if (kv.first == "maxcount") maxcount = std::strtoll(kv.second.c_str(), nullptr, 10);
     else if (kv.first == "outfile") outfile = kv.second;
+    else if (kv.first == "mismatches") mismatches = std::strtoll(kv.second.c_str(), nullptr, 10);
   }
   if (help || !have_genome || !p.positional.empty()) {
     map_usage();
     return -1;
   }
   if (k < 10 || k > 1000) return bail("Error: k-mer length " + std::to_string(k) + " outside 10..1000!");
+  if (mismatches < 0 || mismatches > 2) return bail("Error: number of mismatches " + std::to_string(mismatches) + " outside 0..2!");
   if (maxcount < 0 || maxcount > 0xFFFFFFFFll) return bail("Error: maxcount " + std::to_string(maxcount) + " outside 0..4294967295!");
   if (!file_nonempty(genome)) return bail("Error: Genome does not exist!");
   std::vector<uint32_t> seqlen;
@@ -119,9 +125,9 @@ int mappability_main(int argc, char** argv) {
   if (total != ist.n)
     return bail("Error: the sequence lengths of " + genome + " (" + std::to_string(total - 1) + " characters with separators) do not match the index " +
                 fm9 + " (" + std::to_string(ist.n - 1) + ")!");
-  dg_map_params mp = {(uint32_t)k, forward ? 1 : 0, (uint32_t)maxcount, 0u};
+  dg_map_mm_params mp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, 0u};
   dg_map* m = nullptr;
-  if (dg_mappability(ix, &mp, &m) != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
+  if (dg_mappability_mm(ix, &mp, &m) != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
   struct MapFreer {
     dg_map* m;
     ~MapFreer() { dg_map_free(m); }

@@ -10,6 +10,8 @@
 //   3. reverse strand k_heads: one backward search of revcomp(w) per group head (K-mer table first, left at the first empty
 //                     interval); the head's slot of the start array then holds the group's total
 //   4. scatter        k_scatter: every rank reads its head's total (a broadcast in rank order) and writes it at SA[i]
+// With e = 1 or 2 mismatches (dg_mappability_mm, (k,e)-mappability) phases 1, 2 and 4 are the same and phase 3 is k_heads_mm (map_mm.hpp):
+// per group head a backward search with a mismatch budget of w and of revcomp(w), launched per chunk of head ranks.
 // Transient HBM: the start array (4n) and three bitmaps (3n/8) beside the result (4n), which the end scan uses first.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
@@ -18,7 +20,10 @@
 
 #include <algorithm>
 
+#include <vector>
+
 #include "devfm.hpp"
+#include "experiments.hpp"
 #include "index_internal.hpp"
 
 struct dg_map {
@@ -27,6 +32,7 @@ struct dg_map {
   uint64_t n = 0;                // index n; values cover positions [0, n-1)
   uint32_t* out = nullptr;       // u32[n] (the entry at n-1, the sentinel, is 0)
   dg_map_stats_t st{};
+  dg_map_mm_stats_t mm{};  // all zero for an exact map
   dg::DevBuf run_flags, run_pos, run_val, run_cnt;  // dg_map_runs workspaces (grow-only)
   ~dg_map() {
     (void)hipSetDevice(device);
@@ -193,6 +199,10 @@ __global__ void __launch_bounds__(256) k_heads(FmView f, u32 k, int forward_only
   wave_add(steps, n_ext);  // (every lane of the wavefront is here)
 }
 
+}  // namespace dg
+#include "map_mm.hpp"  // k_heads' sibling for e >= 1 mismatches
+namespace dg {
+
 // out[SA[i]] = the total of i's group (heads hold it in their own slot; members hold their head's rank), 0 for invalid ranks
 __global__ void k_scatter(FmView f, const u64* hd, const u32* start, u32 max_count, u32* out) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -228,7 +238,11 @@ static bool any_lane_busy(dg_index* ix) {  // as hunt.hip's
   return false;
 }
 
-static int map_impl(dg_index* ix, const dg_map_params* prm, dg_map* m) {
+// default ranks per k_heads_mm launch and default W (rows verified on the text): DESIGN.md §10 has the measurements behind both
+static constexpr u64 MM_HEAD_CHUNK = 1ULL << 24;
+static constexpr u32 MM_NARROW = 8;
+
+static int map_impl(dg_index* ix, const dg_map_params* prm, u32 mismatches, dg_map* m) {
   const FmView& f = ix->view;
   const u64 n = f.n;
   const u32 k = prm->k;
@@ -265,7 +279,7 @@ static int map_impl(dg_index* ix, const dg_map_params* prm, dg_map* m) {
   DG_HIP(big_alloc(&b.start, n * 4 + 256, st));
   DG_HIP(big_alloc(&b.bm, 3 * bm_bytes, st));
   DG_HIP(hipMalloc(&b.scan, scan_bytes));
-  DG_HIP(hipMalloc(&b.steps, 8));
+  DG_HIP(hipMalloc(&b.steps, sizeof(MmCounters)));
   u64* acgt = (u64*)b.bm;  // becomes the boundary bitmap once the valid bitmap is made
   u64* valid = acgt + nw;
   u64* hd = valid + nw;
@@ -281,7 +295,7 @@ static int map_impl(dg_index* ix, const dg_map_params* prm, dg_map* m) {
     }
   } evs{ev};
   const u32 TB = 256;
-  DG_HIP(hipMemsetAsync(b.steps, 0, 8, st));
+  DG_HIP(hipMemsetAsync(b.steps, 0, sizeof(MmCounters), st));
   DG_HIP(hipEventRecord(ev[0], st));
   hipLaunchKernelGGL(k_acgt_bits, dim3(ceil_div(nw, TB)), dim3(TB), 0, st, f.text, n, acgt, nw);
   DG_HIP(hipMemsetAsync(valid + nw_data, 0, (nw - nw_data) * 8, st));
@@ -291,12 +305,47 @@ static int map_impl(dg_index* ix, const dg_map_params* prm, dg_map* m) {
   DG_HIP(rocprim::inclusive_scan(b.scan, scan1, rocprim::make_transform_iterator(cnt0, StartKey{bd}), start, (size_t)n, MaxU32(), st));
   DG_HIP(rocprim::inclusive_scan(b.scan, scan2, rocprim::make_transform_iterator(cnt0, EndKey{bd, n}), end_rev, (size_t)n, MinU32(), st));
   DG_HIP(hipEventRecord(ev[2], st));
-  hipLaunchKernelGGL(k_heads, dim3(ceil_div(n, TB)), dim3(TB), 0, st, f, k, prm->forward_only, (const u64*)hd, start, (const u32*)end_rev,
-                     (unsigned long long*)b.steps);
+  u64 launches = 0;
+  std::vector<hipEvent_t> lev;  // DICEY_TIMING: one event per launch, for the longest one
+  struct LaunchEvs {
+    std::vector<hipEvent_t>& v;
+    ~LaunchEvs() {
+      for (hipEvent_t e : v) (void)hipEventDestroy(e);
+    }
+  } levs{lev};
+  if (mismatches == 0) {
+    hipLaunchKernelGGL(k_heads, dim3(ceil_div(n, TB)), dim3(TB), 0, st, f, k, prm->forward_only, (const u64*)hd, start, (const u32*)end_rev,
+                       (unsigned long long*)b.steps);
+  } else {
+    // head ranks in chunks, one launch each: no single launch holds the device for long
+    u64 chunk = MM_HEAD_CHUNK;
+    u32 W = MM_NARROW;
+    if (const char* e = exp_env("DICEY_MAP_HEAD_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
+    if (const char* e = exp_env("DICEY_MAP_NARROW")) W = (u32)std::min<u64>(std::strtoull(e, nullptr, 10), 0xFFFFFFFFull);
+    const bool timing = std::getenv("DICEY_TIMING") != nullptr;
+    MmCounters* ctr = (MmCounters*)b.steps;
+    for (u64 r0 = 0; r0 < n; r0 += chunk, ++launches) {
+      const u64 r1 = std::min(n, r0 + chunk);
+      if (timing) {
+        hipEvent_t e;
+        DG_HIP(hipEventCreate(&e));
+        lev.push_back(e);
+        DG_HIP(hipEventRecord(e, st));
+      }
+      if (mismatches == 1)
+        hipLaunchKernelGGL(k_heads_mm<1>, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, k, prm->forward_only, W, prm->max_count, r0, r1, (const u64*)hd,
+                           start, ctr);
+      else
+        hipLaunchKernelGGL(k_heads_mm<2>, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, k, prm->forward_only, W, prm->max_count, r0, r1, (const u64*)hd,
+                           start, ctr);
+    }
+  }
   DG_HIP(hipEventRecord(ev[3], st));
   hipLaunchKernelGGL(k_scatter, dim3(ceil_div(n, TB)), dim3(TB), 0, st, f, (const u64*)hd, (const u32*)start, prm->max_count, m->out);
   DG_HIP(hipEventRecord(ev[4], st));
-  DG_HIP(hipMemcpyAsync(&m->st.rev_steps, b.steps, 8, hipMemcpyDeviceToHost, st));
+  MmCounters hc{};
+  if (mismatches == 0) DG_HIP(hipMemcpyAsync(&m->st.rev_steps, b.steps, 8, hipMemcpyDeviceToHost, st));
+  else DG_HIP(hipMemcpyAsync(&hc, b.steps, sizeof hc, hipMemcpyDeviceToHost, st));
   DG_HIP(hipStreamSynchronize(st));
   DG_HIP(hipGetLastError());
   float ms[4] = {0, 0, 0, 0};
@@ -307,6 +356,26 @@ static int map_impl(dg_index* ix, const dg_map_params* prm, dg_map* m) {
   m->st.ms_scatter = ms[3];
   m->st.ms_total = ms[0] + ms[1] + ms[2] + ms[3];
   m->st.transient_bytes = n * 4 + 256 + 3 * bm_bytes + scan_bytes;
+  if (mismatches) {
+    m->st.rev_steps = hc.steps;
+    m->mm.heads = hc.heads;
+    m->mm.steps = hc.steps;
+    m->mm.table_reads = hc.table_reads;
+    m->mm.verified_rows = hc.verified_rows;
+    m->mm.early_exits = hc.early_exits;
+    m->mm.launches = launches;
+    m->mm.ms_search = ms[2];
+    if (!lev.empty()) {
+      float longest = 0;
+      for (size_t j = 0; j < lev.size(); ++j) {
+        float t = 0;
+        DG_HIP(hipEventElapsedTime(&t, lev[j], j + 1 < lev.size() ? lev[j + 1] : ev[3]));
+        longest = std::max(longest, t);
+      }
+      std::fprintf(stderr, "dicey timing: mappability e=%u: %llu launches of the head search, %.1f ms in all, longest %.1f ms\n", mismatches,
+                   (unsigned long long)launches, ms[2], longest);
+    }
+  }
   return DG_OK;
 }
 
@@ -316,10 +385,7 @@ using namespace dg;
 
 extern "C" {
 
-int dg_mappability(dg_index* ix, const dg_map_params* p, dg_map** out) {
-  if (out) *out = nullptr;
-  if (!ix || !p || !out) return fail(DG_EINVAL, "dg_mappability: null argument");
-  if (p->flags) return fail(DG_EINVAL, "dg_mappability: flags must be 0");
+static int map_open(dg_index* ix, const dg_map_params* p, u32 mismatches, dg_map** out) {
   if (p->k < 10 || p->k > 1000) return fail(DG_ELIMIT, "dg_mappability: k = %u outside 10..1000", p->k);
   if (ix->view.n < 2 || ix->view.n > 0xFFFFFFFFull) return fail(DG_ELIMIT, "dg_mappability: index of %llu suffixes", (unsigned long long)ix->view.n);
   if (any_lane_busy(ix)) return fail(DG_EINVAL, "dg_mappability: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)");
@@ -333,12 +399,35 @@ int dg_mappability(dg_index* ix, const dg_map_params* p, dg_map** out) {
     delete m;
     return fail(DG_EHIP, "dg_mappability: cannot create a stream");
   }
-  const int rc = map_impl(ix, p, m);
+  const int rc = map_impl(ix, p, mismatches, m);
   if (rc != DG_OK) {
     delete m;
     return rc;
   }
   *out = m;
+  return DG_OK;
+}
+
+int dg_mappability(dg_index* ix, const dg_map_params* p, dg_map** out) {
+  if (out) *out = nullptr;
+  if (!ix || !p || !out) return fail(DG_EINVAL, "dg_mappability: null argument");
+  if (p->flags) return fail(DG_EINVAL, "dg_mappability: flags must be 0");
+  return map_open(ix, p, 0, out);
+}
+
+int dg_mappability_mm(dg_index* ix, const dg_map_mm_params* p, dg_map** out) {
+  if (out) *out = nullptr;
+  if (!p || !out) return fail(DG_EINVAL, "dg_mappability_mm: null argument");
+  if (p->flags || p->reserved) return fail(DG_EINVAL, "dg_mappability_mm: flags and reserved must be 0");
+  if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_mappability_mm: %u mismatches outside 0..2", p->mismatches);
+  if (!ix) return fail(DG_EINVAL, "dg_mappability_mm: null argument");
+  const dg_map_params q = {p->k, p->forward_only, p->max_count, 0u};
+  return map_open(ix, &q, p->mismatches, out);
+}
+
+int dg_map_mm_stats(const dg_map* m, dg_map_mm_stats_t* out) {
+  if (!m || !out) return fail(DG_EINVAL, "dg_map_mm_stats: null argument");
+  *out = m->mm;
   return DG_OK;
 }
 

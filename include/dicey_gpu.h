@@ -39,7 +39,8 @@ extern "C" {
  * 5: dg_hunt_params grows by max_query_len and flags; DG_HUNT_COMPACT: 8 + 4 d bytes per hit and 8 bytes per query cross PCIe / xGMI
  *    (dg_chit_unpack, dg_hunt_expand, dg_normalize_query turn them back); dg_hunt_submit keeps up to three batches in flight on ONE handle
  * 6: dg_hunt_result grows by stream / d_block / d_block_bytes (the gather over RCCL lives in libdiceygather.so, include/dicey_gather.h)
- * 7 (additive exports, same version): dg_mappability, dg_map_values, dg_map_runs, dg_map_device_values, dg_map_stats, dg_map_free */
+ * 7 (additive exports, same version): dg_mappability, dg_map_values, dg_map_runs, dg_map_device_values, dg_map_stats, dg_map_free
+ * 7 (additive exports, same version): dg_mappability_mm, dg_map_mm_stats ((k,e)-mappability, up to two mismatches) */
 #define DG_ABI_VERSION 7
 
 enum {
@@ -465,6 +466,39 @@ int dg_map_runs(dg_map* m, uint64_t lo, uint64_t hi, uint64_t* nruns, uint64_t**
 const void* dg_map_device_values(const dg_map* m);
 int dg_map_stats(const dg_map* m, dg_map_stats_t* out);
 void dg_map_free(dg_map* m); /* NULL: no-op */
+
+/* ABI 7, additive.  (k,e)-mappability, the definition of GEM and GenMap restricted to substitutions: a window q is VALID when T[q, q+k)
+ * lies inside the text and holds only A/C/G/T (the rule above).  For a valid p with w = T[p, p+k) and e = mismatches in 0..2 (else
+ * DG_ELIMIT):
+ *   fwd_e(p) = #{valid q : Hamming(T[q, q+k), w) <= e}  (q = p included),   rev_e(p) = the same against revcomp(w),
+ *   value_e(p) = fwd_e(p) + rev_e(p)   (forward_only: fwd_e(p)),
+ * i.e. the sum of sdsl::count(u) over all u in {A,C,G,T}^k within Hamming distance e of w, and of revcomp(w).  A window that holds N,
+ * an IUPAC letter or '\n' is never an occurrence; a reverse-complement (near-)palindrome is counted on both strands; invalid p has
+ * value 0; sums saturate at 0xFFFFFFFF; max_count = C > 0 writes min(value, C), and the search of a k-mer stops once its total reaches
+ * C.  mismatches = 0 is dg_mappability, bit for bit.  The result is an ordinary dg_map: dg_map_values / dg_map_runs /
+ * dg_map_device_values / dg_map_stats (search time in ms_reverse, backward-search steps in rev_steps) / dg_map_free serve it.  Memory
+ * and the refusal while a hunt batch is in flight are dg_mappability's.  The parameter block is checked before the handle: non-zero
+ * flags or reserved DG_EINVAL, mismatches > 2 DG_ELIMIT, then a null handle DG_EINVAL; *out is cleared on every failure. */
+typedef struct {
+  uint32_t k;           /* k-mer length, 10..1000 */
+  uint32_t mismatches;  /* e: 0, 1 or 2 substitutions */
+  int32_t forward_only; /* fwd_e only */
+  uint32_t max_count;   /* 0 = exact values, else min(value, max_count) */
+  uint32_t flags;       /* 0 */
+  uint32_t reserved;    /* 0 */
+} dg_map_mm_params;
+int dg_mappability_mm(dg_index* ix, const dg_map_mm_params* p, dg_map** out);
+/* counters of the search per group head of equal k-mers (all zero for a map made with mismatches = 0 or by dg_mappability) */
+typedef struct {
+  uint64_t heads;         /* distinct valid k-mers searched */
+  uint64_t steps;         /* backward-search steps (one pair of Occ lines each, all four characters) */
+  uint64_t table_reads;   /* K-mer table entries read */
+  uint64_t verified_rows; /* suffix-array rows finished on the text */
+  uint64_t early_exits;   /* heads whose search stopped at max_count */
+  uint64_t launches;      /* kernel launches of the search (head ranks go through in chunks) */
+  double ms_search;       /* device time of the search */
+} dg_map_mm_stats_t;
+int dg_map_mm_stats(const dg_map* m, dg_map_mm_stats_t* out);
 
 const char* dg_last_error(void);
 int dg_abi_version(void);

@@ -2,7 +2,8 @@
 """Whole-genome timing of dg_mappability (include/dicey_gpu.h) and of `dicey mappability -o` — not the headline bench.  The genome
 is bench.py's synthetic GRCh38-size text (--genome iid | repeats), generated on the device from a seed and indexed with
 dg_index_build_device, or an existing index (--fm9).  Per k: device phase times from HIP events (dg_map_stats), both strands and
-forward only.  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
+forward only; with --mismatches 1|2 the runs go through dg_mappability_mm ((k,e)-mappability) and report the search counters of
+dg_map_mm_stats per head.  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
 Prints one JSON line."""
 import argparse, ctypes as C, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,7 +17,11 @@ ap.add_argument("--genome-size", type=float, default=3.1e9)
 ap.add_argument("--genome", choices=["iid", "repeats"], default="iid")
 ap.add_argument("--fm9", default="", help="reuse this index (its .lens.json beside it holds the sequence lengths)")
 ap.add_argument("--ks", default="24,36,50,100,150")
-ap.add_argument("--cli-k", type=int, default=100)
+ap.add_argument("--mismatches", type=int, default=0, help="e of (k,e)-mappability: 0 (exact), 1 or 2")
+ap.add_argument("--maxcount", type=int, default=0, help="max_count of the runs (0 = exact values)")
+ap.add_argument("--forward", choices=["both", "no", "yes"], default="both", help="which strand settings to time")
+ap.add_argument("--keep-index", action="store_true", help="leave the generated index (and its .lens.json) in --workdir for --fm9 runs")
+ap.add_argument("--cli-k", type=int, default=100, help="k of the end-to-end CLI run; 0 skips it")
 ap.add_argument("--workdir", default="/dev/shm")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -38,40 +43,59 @@ out["open_s"] = round(time.time() - t0, 2)
 n = ix.size()
 out["n"] = n
 runs = []
+LINES_PER_S = 28e9  # what the search kernel sustains in random 64-byte lines: the yardstick of `line_share`
 for k in [int(x) for x in a.ks.split(",")]:
-    for fo in (False, True):
-        prm = _capi.MapParams(k, 1 if fo else 0, 0, 0)
+    for fo in {"both": (False, True), "no": (False,), "yes": (True,)}[a.forward]:
         m = C.c_void_p()
         t0 = time.time()
-        _capi.check(L, L.dg_mappability(ix.handle, C.byref(prm), C.byref(m)))
+        if a.mismatches:
+            prm = _capi.MapMmParams(k, a.mismatches, 1 if fo else 0, a.maxcount, 0, 0)
+            _capi.check(L, L.dg_mappability_mm(ix.handle, C.byref(prm), C.byref(m)))
+        else:
+            prm = _capi.MapParams(k, 1 if fo else 0, a.maxcount, 0)
+            _capi.check(L, L.dg_mappability(ix.handle, C.byref(prm), C.byref(m)))
         wall = time.time() - t0
         st = _capi.MapStats()
         _capi.check(L, L.dg_map_stats(m, C.byref(st)))
+        mm = _capi.MapMmStats()
+        _capi.check(L, L.dg_map_mm_stats(m, C.byref(mm)))
         L.dg_map_free(m)
-        runs.append({"k": k, "forward_only": fo, "ms_total": round(st.ms_total, 1), "ms_valid": round(st.ms_valid, 1),
+        runs.append({"k": k, "mismatches": a.mismatches, "max_count": a.maxcount, "forward_only": fo, "ms_total": round(st.ms_total, 1),
+                     "ms_valid": round(st.ms_valid, 1),
                      "ms_forward": round(st.ms_forward, 1), "ms_reverse": round(st.ms_reverse, 1), "ms_scatter": round(st.ms_scatter, 1),
                      "forward_share": round((st.ms_valid + st.ms_forward + st.ms_scatter) / max(st.ms_total, 1e-9), 3),
                      "rev_steps": st.rev_steps, "wall_s": round(wall, 2), "transient_gb": round(st.transient_bytes / 1e9, 2)})
+        if a.mismatches:
+            h = max(mm.heads, 1)
+            # random lines: two Occ lines per step, one table line per read, per verified row one suffix-array line and the text lines
+            # of the remaining characters (at least one)
+            lines = 2 * mm.steps + mm.table_reads + 2 * mm.verified_rows
+            runs[-1].update({"heads": mm.heads, "launches": mm.launches, "early_exits": mm.early_exits, "ms_search": round(mm.ms_search, 1),
+                             "steps_per_head": round(mm.steps / h, 2), "table_reads_per_head": round(mm.table_reads / h, 2),
+                             "verified_rows_per_head": round(mm.verified_rows / h, 2), "lines_per_head": round(lines / h, 1),
+                             "line_share": round(lines / max(mm.ms_search, 1e-9) * 1e3 / LINES_PER_S, 3)})
         print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
 out["runs"] = runs
 ix.close()
 # the CLI end to end: open + map + runs + format + gzip
 stem = os.path.join(a.workdir, "dicey_map_bench_cli_%s" % a.genome)
-with open(stem + ".fa", "w") as f:
-    f.write(">chr1\nN\n")
-with open(stem + ".fa.fai", "w") as f:
-    for i, l in enumerate(lens):
-        f.write("chr%d\t%d\t0\t60\t61\n" % (i + 1, l))
-if os.path.lexists(stem + ".fm9"):
-    os.remove(stem + ".fm9")
-os.symlink(os.path.abspath(fm9), stem + ".fm9")
 gz = stem + ".bedgraph.gz"
-t0 = time.time()
-r = subprocess.run([os.path.join(ROOT, "dicey_amd", "dicey"), "mappability", "-g", stem + ".fa", "-k", str(a.cli_k), "-o", gz],
-                   capture_output=True, text=True)
-out["cli"] = {"k": a.cli_k, "rc": r.returncode, "wall_s": round(time.time() - t0, 2),
-              "gz_bytes": os.path.getsize(gz) if os.path.exists(gz) else 0, "stderr": r.stderr[-300:]}
-for p in (gz, stem + ".fm9", stem + ".fa", stem + ".fa.fai") + (() if a.fm9 else (fm9, fm9 + ".lens.json")):
+if a.cli_k:
+    with open(stem + ".fa", "w") as f:
+        f.write(">chr1\nN\n")
+    with open(stem + ".fa.fai", "w") as f:
+        for i, l in enumerate(lens):
+            f.write("chr%d\t%d\t0\t60\t61\n" % (i + 1, l))
+    if os.path.lexists(stem + ".fm9"):
+        os.remove(stem + ".fm9")
+    os.symlink(os.path.abspath(fm9), stem + ".fm9")
+    t0 = time.time()
+    r = subprocess.run([os.path.join(ROOT, "dicey_amd", "dicey"), "mappability", "-g", stem + ".fa", "-k", str(a.cli_k), "-e", str(a.mismatches), "-c", str(a.maxcount),
+                        "-o", gz],
+                       capture_output=True, text=True)
+    out["cli"] = {"k": a.cli_k, "mismatches": a.mismatches, "max_count": a.maxcount, "rc": r.returncode, "wall_s": round(time.time() - t0, 2),
+                  "gz_bytes": os.path.getsize(gz) if os.path.exists(gz) else 0, "stderr": r.stderr[-300:]}
+for p in (gz, stem + ".fm9", stem + ".fa", stem + ".fa.fai") + (() if a.fm9 or a.keep_index else (fm9, fm9 + ".lens.json")):
     if os.path.lexists(p):
         os.remove(p)
 print(json.dumps(out))
