@@ -1199,11 +1199,20 @@ int silica(int argc, char** argv) {
   if (fatal) return finish(1);
   const uint32_t nseq = (uint32_t)seqlen.size();
   std::vector<std::vector<PrimerBind>> forBind(nseq), revBind(nseq);
-  if (!pSeq.empty()) {
+  // A primer over 64 nt is more than the library stores, and more than thal() takes (both oligos over 60 nt: silica.h:438-442 ends the
+  // run there with the error JSON).  The primers before it are searched as usual, for the warnings they add ahead of the error.
+  size_t nsearch = pSeq.size();
+  for (size_t q = 0; q < pSeq.size(); ++q)
+    if (pSeq[q].size() > 64) {
+      nsearch = q;
+      break;
+    }
+  const bool over_limit = nsearch < pSeq.size();
+  if (nsearch) {
     std::string pb;
     std::vector<uint64_t> poff(1, 0);
-    for (auto& s : pSeq) {
-      pb += s;
+    for (size_t q = 0; q < nsearch; ++q) {
+      pb += pSeq[q];
       poff.push_back(pb.size());
     }
     dg_search_params sp;
@@ -1214,7 +1223,7 @@ int silica(int argc, char** argv) {
     sp.kmer = c.kmer;
     sp.cut_temp = c.cutTemp;
     dg_search_result* R = nullptr;
-    if (dg_search_sites(ix, th, &sp, seqlen.data(), nseq, (const uint8_t*)pb.data(), poff.data(), pSeq.size(), &R) != DG_OK) {
+    if (dg_search_sites(ix, th, &sp, seqlen.data(), nseq, (const uint8_t*)pb.data(), poff.data(), nsearch, &R) != DG_OK) {
       std::cerr << "dicey: " << dg_last_error() << std::endl;
       dg_thal_close(th);
       dg_index_close(ix);
@@ -1222,7 +1231,7 @@ int silica(int argc, char** argv) {
     }
     // per primer in order: a thal failure ends the run with the error JSON (silica.h:438-442, 512-516)
     uint64_t si = 0;
-    for (size_t q = 0; q < pSeq.size(); ++q) {
+    for (size_t q = 0; q < nsearch; ++q) {
       if (R->pflags[q] & DG_P_THAL_FAILED) {
         msg.push_back("Error: Thermodynamical calculation failed!");
         dg_search_result_free(R);
@@ -1250,6 +1259,10 @@ int silica(int argc, char** argv) {
       }
     }
     dg_search_result_free(R);
+  }
+  if (over_limit) {
+    msg.push_back("Error: Thermodynamical calculation failed!");
+    return finish(1);
   }
   for (uint32_t r = 0; r < nseq; ++r) {  // silica.h:581-584
     allp.insert(allp.end(), forBind[r].begin(), forBind[r].end());

@@ -3,6 +3,7 @@
 #include <dlfcn.h>
 
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -246,6 +247,13 @@ struct orc_search_params {
   uint64_t max_locations;
 };
 
+static std::string& last_search_log() {  // one per process, overwritten by the next orc_search call: single-threaded use only
+  static std::string s;
+  return s;
+}
+static bool g_accept_len_k = false;
+void orc_search_accept_len_k(int on) { g_accept_len_k = on != 0; }
+
 // silica.h:355-640 + writer :100-187.  thal_fn / dump_fn come from oracle/_ref (the reference's own thal.h / json.hpp).
 char* orc_search(void* h, const uint32_t* seqlen, const char* const* seqname, uint32_t nseq, const char* text, uint64_t textlen,
                  const orc_search_params* p, const char* genome, const char* outfile, const char* fasta, void* thal_fn, void* dump_fn,
@@ -258,6 +266,7 @@ char* orc_search(void* h, const uint32_t* seqlen, const char* const* seqname, ui
   r.text = &T;
   r.thal = (ThalFn)thal_fn;
   r.dump_double = (DumpDoubleFn)dump_fn;
+  r.accept_len_k = g_accept_len_k;
   r.c.indel = !p->hamming;
   r.c.pruneprimer = p->pruneprimer != 0;
   r.c.cutTemp = p->cutTemp;
@@ -285,8 +294,25 @@ char* orc_search(void* h, const uint32_t* seqlen, const char* const* seqname, ui
   int code = 0;
   std::string js = r.run(lines, code);
   if (rc) *rc = code;
+  std::string& log = last_search_log();
+  log.clear();
+  char buf[160];
+  for (const auto& h : r.located) {  // doubles as hexadecimal floats: exact
+    std::snprintf(buf, sizeof buf, "H\t%u\t%u\t%llu\t%u\t%u\t%a\n", h.primerId, h.fr, (unsigned long long)h.loc, h.len, h.window, h.temp);
+    log += buf;
+  }
+  for (const auto& b : r.pushed) {
+    std::snprintf(buf, sizeof buf, "P\t%u\t%u\t%u\t%d\t%a\t%a\t", b.refIndex, b.pos, b.primerId, b.onFor ? 1 : 0, b.temp, b.perfTemp);
+    log += buf;
+    log += b.genome;
+    log.push_back('\n');
+  }
   return dup_out(js, json_len);
 }
+
+// the located hits ("H primer strand textpos length window Tm") and the binding sites in push order ("P ref pos primer onFor Tm
+// MatchTm genome") of the last orc_search call of this process
+char* orc_search_log(uint64_t* len) { return dup_out(last_search_log(), len); }
 
 struct orc_padlock_params {
   int32_t json, hamming, probe_mode, overlapping, compute_all, input_fasta, absent;

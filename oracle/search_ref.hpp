@@ -52,6 +52,16 @@ struct SearchRun {
   ThalFn thal;
   DumpDoubleFn dump_double;
   SearchParams c;
+  // what the JSON cannot show (it is sorted by Tm): every located hit that reached thal() and every binding site in the order of the
+  // push_back calls (primer-major, forward k-mer first), for the tests that pin the library's hit count and push order
+  struct LocatedHit {
+    uint32_t primerId, fr, len, window;
+    uint64_t loc;
+    double temp;
+  };
+  bool accept_len_k = false;  // test aid: take a record of exactly k letters too (the reader's `size() > kmer` below), koffset 0
+  std::vector<LocatedHit> located;
+  std::vector<PrimerBind> pushed;
 
   std::string num(double x) const {
     char b[64];
@@ -177,7 +187,7 @@ struct SearchRun {
     for (const std::string& line : lines) {
       if (line.empty()) continue;
       if (line[0] == '>') {
-        if (!fan.empty() && !tmpfasta.empty() && tmpfasta.size() > c.kmer) {
+        if (!fan.empty() && !tmpfasta.empty() && (tmpfasta.size() > c.kmer || (accept_len_k && tmpfasta.size() == c.kmer))) {
           if (!take()) {
             fail = true;
             break;
@@ -191,7 +201,7 @@ struct SearchRun {
         tmpfasta += up;
       }
     }
-    if (!fail && !fan.empty() && !tmpfasta.empty() && tmpfasta.size() > c.kmer)
+    if (!fail && !fan.empty() && !tmpfasta.empty() && (tmpfasta.size() > c.kmer || (accept_len_k && tmpfasta.size() == c.kmer)))
       if (!take()) fail = true;
     if (fail) {
       rc = 1;
@@ -259,6 +269,7 @@ struct SearchRun {
               rc = 1;
               return json(allp, pcrColl, pName, pSeq, msg, c.distance);
             }
+            located.push_back(LocatedHit{primerId, fr, (uint32_t)m, (uint32_t)genomicseq.size(), loc[i], tt});
             if (tt > c.cutTemp) {
               uint32_t alignpos = chrpos;
               Alignment al;
@@ -292,6 +303,7 @@ struct SearchRun {
                 prim.onFor = !fr;
                 prim.pos = chrpos;
                 (fr ? revBind : forBind)[ref].push_back(prim);
+                pushed.push_back(prim);
               }
             }
             ++hits;

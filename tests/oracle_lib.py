@@ -96,6 +96,8 @@ def lib():
                                  C.POINTER(SearchParams), C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
         L.orc_search.restype = C.c_void_p
+        L.orc_search_log.argtypes = [C.POINTER(C.c_uint64)]
+        L.orc_search_log.restype = C.c_void_p
         L.orc_use_ref_json.argtypes = [C.c_char_p]
         _lib = L
         # every JSON object of the writers through the reference's own nlohmann::json when oracle/_ref has it
@@ -270,9 +272,11 @@ class Index:
 
     def search(self, seqlen, seqname, text: bytes, fasta: str, genome="", outfile="", hamming=False, pruneprimer=None,
                cutTemp=45.0, maxProdSize=15000, cutofPen=-1.0, penDiff=0.6, penMis=0.4, penLen=0.001, kmer=15, distance=1,
-               maxNeighborhood=10000, max_locations=10000):
+               maxNeighborhood=10000, max_locations=10000, want_log=False):
         """`dicey search` through the restated silica.h driver + the reference's own thal()/json dump (oracle/_ref).
-        Returns (json_text, exit_code)."""
+        Returns (json_text, exit_code); with want_log also (located, pushed): every located hit that reached thal() as
+        (primer, strand, text position, length, window length, Tm) and every binding site in the order of the reference's
+        push_back calls as (ref, pos, primer, on_for, Tm, MatchTm, genome) — the JSON holds the sites sorted by Tm."""
         libs = ref_libs()
         if libs is None:
             raise RuntimeError("oracle/_ref is not built")
@@ -287,7 +291,18 @@ class Index:
         jf = C.cast(J.ref_json_dump_double, C.c_void_p)
         jp = lib().orc_search(self.h, sl, sn, nseq, text, len(text), C.byref(p), genome.encode(), outfile.encode(), fasta.encode(),
                               tf, jf, C.byref(rc), C.byref(jl))
-        return _take(jp, jl.value).decode(), rc.value
+        js = _take(jp, jl.value).decode()
+        if not want_log:
+            return js, rc.value
+        ll = C.c_uint64()
+        located, pushed = [], []
+        for ln in _take(lib().orc_search_log(C.byref(ll)), ll.value).decode("latin-1").split("\n")[:-1]:
+            f = ln.split("\t")
+            if f[0] == "H":
+                located.append((int(f[1]), int(f[2]), int(f[3]), int(f[4]), int(f[5]), float.fromhex(f[6])))
+            else:
+                pushed.append((int(f[1]), int(f[2]), int(f[3]), f[4] == "1", float.fromhex(f[5]), float.fromhex(f[6]), f[7]))
+        return js, rc.value, located, pushed
 
     def padlock(self, chrname, chrseq, gtf_text: str, barcodes_text: str, genes=(), compute_all=False, input_fasta=False, absent=False,
                 json=False, hamming=False, probe_mode=False, overlapping=False, distance=1, armlen=20, tmdiff=2, gcmin=0.4, gcmax=0.6,

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Randomised differential run of `dicey search` (the repo's binary) against the oracle (restated silica.h + the reference's
-own thal.h, oracle/_ref) on a small repeat-rich genome: random primer sets and option combinations; JSON must be identical."""
+own thal.h, oracle/_ref) on a small repeat-rich genome: random primer sets and option combinations; JSON must be identical.
+A third argument `wide` draws from the wider ranges the site stage has paths of its own for (primers of 16-60 nt, k 10-30,
+distance 0-2, -x); without it the stream of configurations is what it always was."""
 import gzip, os, random, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -9,6 +11,7 @@ from conftest import make_genome, genome_text, revcomp
 
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 nconf = int(sys.argv[2]) if len(sys.argv) > 2 else 12
+wide = len(sys.argv) > 3 and sys.argv[3] == "wide"
 rng = random.Random(seed)
 DICEY = os.environ.get("DICEY_BIN", os.path.join(ROOT, "dicey_amd", "dicey"))  # DICEY_BIN: e.g. a tools/hostemu-linked binary
 d = tempfile.mkdtemp(prefix="fuzz_search_")
@@ -37,7 +40,7 @@ for c in range(nconf):
     rec = []
     while len(rec) < rng.randint(6, 30):
         ci, p = rng.randrange(3), rng.randrange(0, 27000)
-        L1, L2, dist = rng.randint(16, 30), rng.randint(16, 30), rng.randint(60, 2500)
+        L1, L2, dist = rng.randint(16, 60 if wide else 30), rng.randint(16, 60 if wide else 30), rng.randint(60, 2500)
         fw, rv = seqs[ci][p:p + L1], revcomp(seqs[ci][p + dist:p + dist + L2])
         if "N" in fw + rv or len(rv) < L2: continue
         for k_ in range(rng.choice([0, 0, 1, 2])):
@@ -50,9 +53,15 @@ for c in range(nconf):
     open(pf, "w").write(fasta)
     args, kw = [], {}
     if rng.random() < 0.4: args += ["-n"]; kw["hamming"] = True
-    if rng.random() < 0.5:
+    if wide:  # a wide k-mer at distance 2 only with Hamming, where the neighbourhood stays small enough for the oracle's enumeration
+        dd = rng.choice([0, 1, 1, 2]); args += ["-d", str(dd)]; kw["distance"] = dd
+        k = rng.randint(10, 15) if dd == 2 and "hamming" not in kw else rng.randint(10, 30)
+        k = min(k, min(len(s_) for _, s_ in rec) - 1); args += ["-k", str(k)]; kw["kmer"] = k
+        if rng.random() < 0.4:
+            x = rng.choice([500, 3000, 20000]); args += ["-x", str(x)]; kw["maxNeighborhood"] = x
+    if not wide and rng.random() < 0.5:
         dd = rng.choice([0, 1]); args += ["-d", str(dd)]; kw["distance"] = dd
-    if rng.random() < 0.6:
+    if not wide and rng.random() < 0.6:
         k = rng.randint(11, 16); args += ["-k", str(k)]; kw["kmer"] = k
     if rng.random() < 0.5:
         ct = rng.choice([35.0, 40.0, 50.0, 55.0]); args += ["-c", str(ct)]; kw["cutTemp"] = ct
