@@ -110,6 +110,9 @@ int dg_padlock_scan(dg_index* ix, dg_thal* th, const dg_padlock_params* p, const
   *out = nullptr;
   const uint64_t L = p->armlen, T = 2 * L;
   if (L == 0) return fail(DG_EINVAL, "dg_padlock_scan: arm length 0");
+  // stage 3 counts neighbourhoods with dg_neighborhood_count, which takes 10 nt or more: refused here, not after two stages of thal
+  if (p->distance > 0 && L < 10)
+    return fail(DG_EINVAL, "dg_padlock_scan: arm length %u with distance %u: neighbourhood counts need arms of 10 nt or more", p->armlen, p->distance);
   ResultBox* box = new ResultBox;
   dg_padlock_result* R = &box->pub;
   std::memset(R, 0, sizeof *R);

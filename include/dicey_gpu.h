@@ -354,7 +354,9 @@ int dg_thal_batch(dg_thal* th, const uint8_t* seqs, const uint64_t* off, size_t 
  *                dg_neighborhood_count); both -1 unless the arm belongs to a probe inside the Tm window (:372-374)
  * The caller replays the reference's decisions (including `k += targetlen - 1` after an accepted probe) on these arrays;
  * a decision that would need a value not computed here cannot be reached.  thal refusing a pair (both oligos > 60 nt)
- * shows as -999999, the reference's error path (:337-340). */
+ * shows as -999999, the reference's error path (:337-340).
+ * armlen < 10 with distance > 0 is refused with DG_EINVAL before any GPU work: the reference enumerates neighbors() of arms
+ * of any length (:396-405, neighbors.h), dg_neighborhood_count takes 10 nt or more.  distance 0 takes every armlen >= 1. */
 #define DG_PADLOCK_NOT_COMPUTED (-1e300)
 typedef struct {
   uint32_t armlen;    /* -m */
