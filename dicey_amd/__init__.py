@@ -164,8 +164,11 @@ class FmIndex:
         k-mer of A/C/G/T starts; min(value, max_count) when max_count > 0.  With mismatches = e in 1..2 the counts are those of
         the windows within Hamming distance e of w and of revcomp(w): (k,e)-mappability.  `stats`, when given, receives the phase
         times and, for e > 0, the search counters (dg_map_mm_stats_t)."""
+        return self._map_array(self._map(k, forward_only, max_count, mismatches), stats, mm=mismatches > 0)
+
+    def _map_array(self, m, stats, mm=False):
+        """the values of a dg_map as a numpy array (and its stats into `stats`); frees the map"""
         import numpy as np
-        m = self._map(k, forward_only, max_count, mismatches)
         try:
             st = _capi.MapStats()
             _capi.check(self._L, self._L.dg_map_stats(m, C.byref(st)))
@@ -173,10 +176,10 @@ class FmIndex:
             _capi.check(self._L, self._L.dg_map_values(m, 0, st.n - 1, out.ctypes.data_as(C.POINTER(C.c_uint32))))
             if stats is not None:
                 stats.update({f: getattr(st, f) for f, _ in _capi.MapStats._fields_ if f != "reserved"})
-                if mismatches > 0:
-                    mm = _capi.MapMmStats()
-                    _capi.check(self._L, self._L.dg_map_mm_stats(m, C.byref(mm)))
-                    stats.update({f: getattr(mm, f) for f, _ in _capi.MapMmStats._fields_})
+                if mm:
+                    ms = _capi.MapMmStats()
+                    _capi.check(self._L, self._L.dg_map_mm_stats(m, C.byref(ms)))
+                    stats.update({f: getattr(ms, f) for f, _ in _capi.MapMmStats._fields_})
             return out
         finally:
             self._L.dg_map_free(m)
@@ -186,6 +189,32 @@ class FmIndex:
         """The same values as maximal runs of equal non-zero values inside text positions [lo, hi) (hi = n-1 when None): numpy
         arrays (start uint64, length uint32, value uint32); a run is cut at lo and hi."""
         m = self._map(k, forward_only, max_count, mismatches)
+        try:
+            if hi is None:
+                st = _capi.MapStats()
+                _capi.check(self._L, self._L.dg_map_stats(m, C.byref(st)))
+                hi = st.n - 1
+            return self._map_runs(m, lo, hi)
+        finally:
+            self._L.dg_map_free(m)
+
+    def _min_unique(self, max_k, forward_only):
+        m = C.c_void_p()
+        prm = _capi.MinUniqueParams(max_k, 1 if forward_only else 0, 0, 0)
+        _capi.check(self._L, self._L.dg_min_unique(self._h, C.byref(prm), C.byref(m)))
+        return m
+
+    def min_unique(self, max_k: int = 100, forward_only: bool = False, stats: Optional[dict] = None):
+        """Minimum unique length of every text position (include/dicey_gpu.h dg_min_unique): numpy uint32 array of n-1 values,
+        value[p] = the smallest k <= min(run of A/C/G/T from p, max_k) at which mappability(k)[p] == 1 (with forward_only: at which
+        the k-mer occurs once on the forward strand), 0 where there is none.  `stats`, when given, receives dg_map_stats_t: the
+        neighbour-prefix pass in ms_forward, the other strand's backward search in ms_reverse and its steps in rev_steps."""
+        return self._map_array(self._min_unique(max_k, forward_only), stats)
+
+    def min_unique_runs(self, max_k: int = 100, forward_only: bool = False, lo: int = 0, hi: Optional[int] = None):
+        """The same lengths as maximal runs of equal non-zero values inside text positions [lo, hi) (hi = n-1 when None): numpy
+        arrays (start uint64, length uint32, value uint32); a run is cut at lo and hi."""
+        m = self._min_unique(max_k, forward_only)
         try:
             if hi is None:
                 st = _capi.MapStats()

@@ -101,6 +101,10 @@ class MapMmStats(C.Structure):
                 ("early_exits", C.c_uint64), ("launches", C.c_uint64), ("ms_search", C.c_double)]
 
 
+class MinUniqueParams(C.Structure):
+    _fields_ = [("max_k", C.c_uint32), ("forward_only", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # every symbol include/dicey_gpu.h declares; tests/test_capi_symbols.py checks the list against the header
 class PadlockParams(C.Structure):
     _fields_ = [("armlen", C.c_uint32), ("distance", C.c_uint32), ("hamming", C.c_int32), ("tmdiff", C.c_uint32),
@@ -122,7 +126,7 @@ SYMBOLS = ["dg_index_open", "dg_index_close", "dg_index_stats", "dg_count", "dg_
            "dg_neighbors", "dg_buffer_free", "dg_hit_rows", "dg_hunt_rows", "dg_hunt_submit", "dg_hunt_wait", "dg_hunt_device_submit",
            "dg_chit_unpack", "dg_normalize_query", "dg_hunt_expand", "dg_index_stream", "dg_fm9_check",
            "dg_mappability", "dg_map_values", "dg_map_runs", "dg_map_device_values", "dg_map_stats", "dg_map_free",
-           "dg_mappability_mm", "dg_map_mm_stats"]
+           "dg_mappability_mm", "dg_map_mm_stats", "dg_min_unique"]
 
 _lib = None
 
@@ -198,6 +202,7 @@ def load(path=None):
     L.dg_map_free.argtypes = [vp]
     L.dg_mappability_mm.argtypes = [vp, C.POINTER(MapMmParams), C.POINTER(vp)]
     L.dg_map_mm_stats.argtypes = [vp, C.POINTER(MapMmStats)]
+    L.dg_min_unique.argtypes = [vp, C.POINTER(MinUniqueParams), C.POINTER(vp)]
     L.dg_map_free.restype = None
     if path is None:
         _lib = L

@@ -2,6 +2,7 @@
 // Not upstream dicey's chop + aligner + mappability pipeline: the value of a position is the number of occurrences of the k-mer that
 // starts there, on both strands, counted on the FM-index in HBM.  The device hands over runs of equal values per position chunk;
 // the host formats the chunks on several threads, compresses them (-o) into concatenated gzip members and writes them in order.
+// With -u the value is the minimum unique length instead (dg_min_unique): the shortest k-mer that starts at the position and is unique.
 #include <zlib.h>
 
 #include <algorithm>
@@ -18,7 +19,7 @@ namespace {
 
 const OptSpec kMapOpts[] = {{"help", '?', false},  {"genome", 'g', true},  {"kmer", 'k', true},
                             {"forward", 'f', false}, {"maxcount", 'c', true}, {"outfile", 'o', true},
-                            {"mismatches", 'e', true}};
+                            {"mismatches", 'e', true}, {"minunique", 'u', false}};
 
 void map_usage() {
   std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz" << std::endl;
@@ -29,6 +30,7 @@ void map_usage() {
                "  -e [ --mismatches ] arg (=0)       count k-mers with up to this many mismatches (0..2)\n"
                "  -f [ --forward ]                   forward strand only\n"
                "  -c [ --maxcount ] arg (=0)         write min(value, maxcount); 0 = exact values\n"
+               "  -u [ --minunique ]                 write the minimum unique length instead; -k is then the largest length tried\n"
                "  -o [ --outfile ] arg               gzipped output file (default: plain text on stdout)\n"
                "\n"
                "Output: bedGraph lines name, start, end, value (0-based, end exclusive) of maximal runs of equal values, where the value\n"
@@ -37,6 +39,9 @@ void map_usage() {
                "character other than A/C/G/T or runs past the sequence end have no line.  With -e 1 or -e 2 the value counts the k-mers\n"
                "of the genome within that many mismatches (substitutions) of the k-mer and of its reverse complement, the k-mer\n"
                "itself included ((k,e)-mappability); k-mers with a character other than A/C/G/T are never counted.\n"
+               "With -u the value of a position is the smallest length k (at most -k, and inside the run of A/C/G/T that starts there) at\n"
+               "which the k-mer that starts there has value 1: it occurs once and its reverse complement nowhere (-f: once on the forward\n"
+               "strand).  Positions without such a length, still repeated at -k or at the end of their run, have no line.\n"
                "\n";
 }
 
@@ -86,7 +91,7 @@ int mappability_main(int argc, char** argv) {
     return -1;
   }
   std::string genome, outfile;
-  bool help = false, have_genome = false, forward = false;
+  bool help = false, have_genome = false, forward = false, minunique = false;
   long long k = 100, maxcount = 0, mismatches = 0;
   for (auto& kv : p.kv) {
     if (kv.first == "help") help = true;
@@ -96,6 +101,7 @@ int mappability_main(int argc, char** argv) {
     else if (kv.first == "maxcount") maxcount = std::strtoll(kv.second.c_str(), nullptr, 10);
     else if (kv.first == "outfile") outfile = kv.second;
     else if (kv.first == "mismatches") mismatches = std::strtoll(kv.second.c_str(), nullptr, 10);
+    else if (kv.first == "minunique") minunique = true;
   }
   if (help || !have_genome || !p.positional.empty()) {
     map_usage();
@@ -104,6 +110,7 @@ int mappability_main(int argc, char** argv) {
   if (k < 10 || k > 1000) return bail("Error: k-mer length " + std::to_string(k) + " outside 10..1000!");
   if (mismatches < 0 || mismatches > 2) return bail("Error: number of mismatches " + std::to_string(mismatches) + " outside 0..2!");
   if (maxcount < 0 || maxcount > 0xFFFFFFFFll) return bail("Error: maxcount " + std::to_string(maxcount) + " outside 0..4294967295!");
+  if (minunique && (mismatches != 0 || maxcount != 0)) return bail("Error: --minunique cannot be combined with --mismatches or --maxcount!");
   if (!file_nonempty(genome)) return bail("Error: Genome does not exist!");
   std::vector<uint32_t> seqlen;
   std::vector<std::string> seqname;
@@ -126,8 +133,9 @@ int mappability_main(int argc, char** argv) {
     return bail("Error: the sequence lengths of " + genome + " (" + std::to_string(total - 1) + " characters with separators) do not match the index " +
                 fm9 + " (" + std::to_string(ist.n - 1) + ")!");
   dg_map_mm_params mp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, 0u};
+  dg_min_unique_params up = {(uint32_t)k, forward ? 1 : 0, 0u, 0u};
   dg_map* m = nullptr;
-  if (dg_mappability_mm(ix, &mp, &m) != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
+  if ((minunique ? dg_min_unique(ix, &up, &m) : dg_mappability_mm(ix, &mp, &m)) != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
   struct MapFreer {
     dg_map* m;
     ~MapFreer() { dg_map_free(m); }

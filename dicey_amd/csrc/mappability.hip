@@ -13,6 +13,8 @@
 // With e = 1 or 2 mismatches (dg_mappability_mm, (k,e)-mappability) phases 1, 2 and 4 are the same and phase 3 is k_heads_mm (map_mm.hpp):
 // per group head a backward search with a mismatch budget of w and of revcomp(w), launched per chunk of head ranks.
 // Transient HBM: the start array (4n) and three bitmaps (3n/8) beside the result (4n), which the end scan uses first.
+// dg_min_unique (min_unique.hpp) answers the inverse question on the same handle type: per position the smallest k at which the value
+// is 1, from one pass over neighbouring suffixes and one backward search per rank.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -354,7 +356,7 @@ static int map_impl(dg_index* ix, const dg_map_params* prm, u32 mismatches, dg_m
   m->st.ms_forward = ms[1];
   m->st.ms_reverse = ms[2];
   m->st.ms_scatter = ms[3];
-  m->st.ms_total = ms[0] + ms[1] + ms[2] + ms[3];
+  m->st.ms_total = (double)ms[0] + (double)ms[1] + (double)ms[2] + (double)ms[3];  // in double: exactly the sum of the reported parts
   m->st.transient_bytes = n * 4 + 256 + 3 * bm_bytes + scan_bytes;
   if (mismatches) {
     m->st.rev_steps = hc.steps;
@@ -380,15 +382,114 @@ static int map_impl(dg_index* ix, const dg_map_params* prm, u32 mismatches, dg_m
 }
 
 }  // namespace dg
+#include "min_unique.hpp"  // the kernels of dg_min_unique
+namespace dg {
+
+// default ranks per launch of the two passes (the same reasoning as MM_HEAD_CHUNK: no launch holds a shared device for long)
+static constexpr u64 MU_CHUNK = 1ULL << 24;
+
+static int min_unique_impl(dg_index* ix, u32 max_k, int forward_only, dg_map* m) {
+  const FmView& f = ix->view;
+  const u64 n = f.n;
+  // the INDEX handle's stream, as map_impl: the passes read the index and are ordered with the handle's other work; the map's own stream
+  // serves dg_map_values / dg_map_runs afterwards (the final synchronize below is the hand-over)
+  hipStream_t st = ix->stream;
+  const u64 lcp_bytes = (n + 1) * 2 + 256;
+  const u64 need = n * 4 + 256 + lcp_bytes + 64;
+  size_t free_b = 0, total_b = 0;
+  DG_HIP(hipMemGetInfo(&free_b, &total_b));
+  if ((u64)free_b < need + (64ULL << 20))
+    return fail(DG_ENOMEM, "dg_min_unique: needs %llu MB of device memory, %llu MB free", (unsigned long long)(need >> 20),
+                (unsigned long long)(free_b >> 20));
+  struct Bufs {
+    hipStream_t st;
+    void *lcp = nullptr, *steps = nullptr;
+    ~Bufs() {
+      (void)hipStreamSynchronize(st);
+      if (lcp) big_free(lcp, st);
+      if (steps) (void)hipFree(steps);
+      (void)hipStreamSynchronize(st);
+    }
+  } b{st};
+  DG_HIP(big_alloc((void**)&m->out, n * 4 + 256, st));
+  DG_HIP(big_alloc(&b.lcp, lcp_bytes, st));
+  DG_HIP(hipMalloc(&b.steps, 8));
+  u64 chunk = MU_CHUNK;
+  if (const char* e = exp_env("DICEY_MAP_HEAD_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
+  const bool timing = std::getenv("DICEY_TIMING") != nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  struct Evs {  // in place before the first event exists: a failed creation releases the earlier ones
+    hipEvent_t* e;
+    ~Evs() {
+      for (int j = 0; j < 3; ++j)
+        if (e[j]) (void)hipEventDestroy(e[j]);
+    }
+  } evs{ev};
+  for (auto& e : ev) DG_HIP(hipEventCreate(&e));
+  std::vector<hipEvent_t> lev;  // DICEY_TIMING: one event per launch of the walk, for the longest one
+  struct LaunchEvs {
+    std::vector<hipEvent_t>& v;
+    ~LaunchEvs() {
+      for (hipEvent_t e : v) (void)hipEventDestroy(e);
+    }
+  } levs{lev};
+  const u32 TB = 256;
+  DG_HIP(hipMemsetAsync(b.steps, 0, 8, st));
+  DG_HIP(hipEventRecord(ev[0], st));
+  for (u64 r0 = 0; r0 < n + 1; r0 += chunk) {  // ranks 0..n: lcp[n] closes the array
+    const u64 r1 = std::min(n + 1, r0 + chunk);
+    hipLaunchKernelGGL(k_mu_lcp, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, max_k, r0, r1, (u16*)b.lcp);
+  }
+  DG_HIP(hipEventRecord(ev[1], st));
+  u64 launches = 0;
+  for (u64 r0 = 0; r0 < n; r0 += chunk, ++launches) {
+    const u64 r1 = std::min(n, r0 + chunk);
+    if (timing) {
+      hipEvent_t e;
+      DG_HIP(hipEventCreate(&e));
+      lev.push_back(e);
+      DG_HIP(hipEventRecord(e, st));
+    }
+    hipLaunchKernelGGL(k_mu_walk, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, max_k, forward_only, r0, r1, (const u16*)b.lcp, m->out,
+                       (unsigned long long*)b.steps);
+  }
+  DG_HIP(hipEventRecord(ev[2], st));
+  DG_HIP(hipMemcpyAsync(&m->st.rev_steps, b.steps, 8, hipMemcpyDeviceToHost, st));
+  DG_HIP(hipStreamSynchronize(st));
+  DG_HIP(hipGetLastError());
+  float ms[2] = {0, 0};
+  for (int j = 0; j < 2; ++j) DG_HIP(hipEventElapsedTime(&ms[j], ev[j], ev[j + 1]));
+  m->st.ms_valid = 0;
+  m->st.ms_forward = ms[0];
+  m->st.ms_reverse = ms[1];
+  m->st.ms_scatter = 0;  // the walk writes the value itself
+  m->st.ms_total = (double)ms[0] + (double)ms[1];  // in double: exactly the sum of the reported parts
+  m->st.transient_bytes = lcp_bytes;
+  if (!lev.empty()) {
+    float longest = 0;
+    for (size_t j = 0; j < lev.size(); ++j) {
+      float t = 0;
+      DG_HIP(hipEventElapsedTime(&t, lev[j], j + 1 < lev.size() ? lev[j + 1] : ev[2]));
+      longest = std::max(longest, t);
+    }
+    std::fprintf(stderr, "dicey timing: min unique max_k=%u: %llu launches of the walk, %.1f ms in all, longest %.1f ms\n", max_k,
+                 (unsigned long long)launches, ms[1], longest);
+  }
+  return DG_OK;
+}
+
+}  // namespace dg
 
 using namespace dg;
 
 extern "C" {
 
-static int map_open(dg_index* ix, const dg_map_params* p, u32 mismatches, dg_map** out) {
-  if (p->k < 10 || p->k > 1000) return fail(DG_ELIMIT, "dg_mappability: k = %u outside 10..1000", p->k);
-  if (ix->view.n < 2 || ix->view.n > 0xFFFFFFFFull) return fail(DG_ELIMIT, "dg_mappability: index of %llu suffixes", (unsigned long long)ix->view.n);
-  if (any_lane_busy(ix)) return fail(DG_EINVAL, "dg_mappability: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)");
+// mode: 0 = dg_mappability / dg_mappability_mm (p->k is k), 1 = dg_min_unique (p->k is max_k)
+static int map_open(dg_index* ix, const dg_map_params* p, u32 mismatches, int mode, dg_map** out) {
+  const char* who = mode ? "dg_min_unique" : "dg_mappability";
+  if (p->k < 10 || p->k > 1000) return fail(DG_ELIMIT, "%s: %s = %u outside 10..1000", who, mode ? "max_k" : "k", p->k);
+  if (ix->view.n < 2 || ix->view.n > 0xFFFFFFFFull) return fail(DG_ELIMIT, "%s: index of %llu suffixes", who, (unsigned long long)ix->view.n);
+  if (any_lane_busy(ix)) return fail(DG_EINVAL, "%s: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)", who);
   DG_HIP(hipSetDevice(ix->device));
   dg_map* m = new dg_map;
   m->device = ix->device;
@@ -397,9 +498,9 @@ static int map_open(dg_index* ix, const dg_map_params* p, u32 mismatches, dg_map
   m->st.k = p->k;
   if (hipStreamCreate(&m->stream) != hipSuccess) {
     delete m;
-    return fail(DG_EHIP, "dg_mappability: cannot create a stream");
+    return fail(DG_EHIP, "%s: cannot create a stream", who);
   }
-  const int rc = map_impl(ix, p, mismatches, m);
+  const int rc = mode ? min_unique_impl(ix, p->k, p->forward_only, m) : map_impl(ix, p, mismatches, m);
   if (rc != DG_OK) {
     delete m;
     return rc;
@@ -412,7 +513,7 @@ int dg_mappability(dg_index* ix, const dg_map_params* p, dg_map** out) {
   if (out) *out = nullptr;
   if (!ix || !p || !out) return fail(DG_EINVAL, "dg_mappability: null argument");
   if (p->flags) return fail(DG_EINVAL, "dg_mappability: flags must be 0");
-  return map_open(ix, p, 0, out);
+  return map_open(ix, p, 0, 0, out);
 }
 
 int dg_mappability_mm(dg_index* ix, const dg_map_mm_params* p, dg_map** out) {
@@ -422,7 +523,17 @@ int dg_mappability_mm(dg_index* ix, const dg_map_mm_params* p, dg_map** out) {
   if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_mappability_mm: %u mismatches outside 0..2", p->mismatches);
   if (!ix) return fail(DG_EINVAL, "dg_mappability_mm: null argument");
   const dg_map_params q = {p->k, p->forward_only, p->max_count, 0u};
-  return map_open(ix, &q, p->mismatches, out);
+  return map_open(ix, &q, p->mismatches, 0, out);
+}
+
+int dg_min_unique(dg_index* ix, const dg_min_unique_params* p, dg_map** out) {
+  if (out) *out = nullptr;
+  if (!p || !out) return fail(DG_EINVAL, "dg_min_unique: null argument");
+  if (p->flags || p->reserved) return fail(DG_EINVAL, "dg_min_unique: flags and reserved must be 0");
+  if (p->max_k < 10 || p->max_k > 1000) return fail(DG_ELIMIT, "dg_min_unique: max_k = %u outside 10..1000", p->max_k);
+  if (!ix) return fail(DG_EINVAL, "dg_min_unique: null argument");
+  const dg_map_params q = {p->max_k, p->forward_only, 0u, 0u};
+  return map_open(ix, &q, 0, 1, out);
 }
 
 int dg_map_mm_stats(const dg_map* m, dg_map_mm_stats_t* out) {

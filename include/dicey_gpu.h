@@ -40,7 +40,8 @@ extern "C" {
  *    (dg_chit_unpack, dg_hunt_expand, dg_normalize_query turn them back); dg_hunt_submit keeps up to three batches in flight on ONE handle
  * 6: dg_hunt_result grows by stream / d_block / d_block_bytes (the gather over RCCL lives in libdiceygather.so, include/dicey_gather.h)
  * 7 (additive exports, same version): dg_mappability, dg_map_values, dg_map_runs, dg_map_device_values, dg_map_stats, dg_map_free
- * 7 (additive exports, same version): dg_mappability_mm, dg_map_mm_stats ((k,e)-mappability, up to two mismatches) */
+ * 7 (additive exports, same version): dg_mappability_mm, dg_map_mm_stats ((k,e)-mappability, up to two mismatches)
+ * 7 (additive exports, same version): dg_min_unique (the shortest unique k-mer at each position) */
 #define DG_ABI_VERSION 7
 
 enum {
@@ -501,6 +502,34 @@ typedef struct {
   double ms_search;       /* device time of the search */
 } dg_map_mm_stats_t;
 int dg_map_mm_stats(const dg_map* m, dg_map_mm_stats_t* out);
+
+/* ABI 7, additive.  Minimum unique length: how long must an oligo that starts at p be before it is unique in the genome?  For the index
+ * text T (sentinel at n-1), a position p in [0, n-1) and max_k in 10..1000 (else DG_ELIMIT):
+ *   run(p)     = the number of consecutive A/C/G/T bytes from p; 0 when T[p] is anything else (N, IUPAC letters, the '\n' between
+ *                sequences and the sentinel all end a run),
+ *   limit(p)   = min(run(p), max_k),
+ *   value_k(p) = dg_mappability's value at k: count(w) + count(revcomp(w)) for w = T[p, p+k), count = sdsl::count (forward_only:
+ *                count(w) alone); a reverse-complement palindrome therefore never has value 1 at its own length,
+ *   mul(p)     = the smallest k in 1..limit(p) with value_k(p) == 1, and 0 when there is none: the position is not A/C/G/T, or the
+ *                k-mer is still repeated at limit(p).
+ * So for every k in 10..max_k and every p whose k-mer is valid at k: mul(p) != 0 && mul(p) <= k  <=>  dg_mappability(k)[p] == 1; and
+ * mul(p) = max(1 + maxlcp(p), first k with count(revcomp(w_k)) == 0) wherever both are <= limit(p), maxlcp(p) being the longer common
+ * prefix (raw text bytes) of suffix p with its neighbours in suffix-array order.  Values below 10 are legal (small genomes).  One
+ * pass over the suffix array instead of one dg_mappability pass per candidate k.  The result is an ordinary dg_map: dg_map_values /
+ * dg_map_runs (a run is a stretch of equal non-zero lengths) / dg_map_device_values / dg_map_free serve it; dg_map_stats has k =
+ * max_k, the neighbour-prefix pass in ms_forward, the backward search of the other strand in ms_reverse with its steps in rev_steps,
+ * ms_valid = ms_scatter = 0 (the search writes the values); dg_map_mm_stats stays all zero.  Like dg_mappability the computation runs on
+ * the index handle's stream (the map's own stream serves the reads afterwards).  Needs about 6n bytes of free HBM beside
+ * the index (DG_ENOMEM before any kernel otherwise); DG_EINVAL while a dg_hunt_submit batch is in flight on the handle.  The parameter
+ * block is checked before the handle: non-zero flags or reserved DG_EINVAL, max_k outside 10..1000 DG_ELIMIT, then a null handle
+ * DG_EINVAL; *out is cleared on every failure. */
+typedef struct {
+  uint32_t max_k;       /* 10..1000 */
+  int32_t forward_only; /* value_k = count(w) alone */
+  uint32_t flags;       /* 0 */
+  uint32_t reserved;    /* 0 */
+} dg_min_unique_params;
+int dg_min_unique(dg_index* ix, const dg_min_unique_params* p, dg_map** out);
 
 const char* dg_last_error(void);
 int dg_abi_version(void);
