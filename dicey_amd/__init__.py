@@ -14,7 +14,9 @@ from typing import List, Optional, Sequence
 from . import _capi
 from ._capi import DgError, DG_Q_DIST_ADJUSTED, DG_Q_MAX_MATCHES, DG_Q_NBHD_EXCEEDED, DG_Q_TOO_SHORT
 
-__all__ = ["FmIndex", "Thal", "search_sites", "DnaHit", "QueryResult", "HuntBatch", "build_index", "DgError"]
+__all__ = ["FmIndex", "Thal", "search_sites", "DnaHit", "QueryResult", "HuntBatch", "build_index", "DgError", "QMAP_INVALID"]
+
+QMAP_INVALID = _capi.DG_QMAP_INVALID  # FmIndex.query_mappability: no k-mer of A/C/G/T starts at the position
 
 
 @dataclass
@@ -223,6 +225,24 @@ class FmIndex:
             return self._map_runs(m, lo, hi)
         finally:
             self._L.dg_map_free(m)
+
+    def query_mappability(self, seqs: Sequence, k: int = 100, forward_only: bool = False, max_count: int = 0, mismatches: int = 0,
+                          stats: Optional[dict] = None):
+        """k-mer counts for sequences that are NOT in the index (include/dicey_gpu.h dg_query_map): a list with one numpy uint32 array
+        per record, value[p] = the number of windows of the genome within Hamming distance `mismatches` (0..2) of the k-mer w at p of the
+        record, plus those within it of revcomp(w) (w alone with forward_only); 0 = absent from the genome; QMAP_INVALID where p + k runs
+        past the record or w holds a byte other than A/C/G/T; min(value, max_count) when max_count > 0.  str records are upper-cased,
+        bytes go through as given.  `stats`, when given, receives dg_qmap_stats_t."""
+        import numpy as np
+        recs = [s.upper().encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        buf, off = _pack(recs)
+        out = np.zeros(len(buf), dtype=np.uint32)
+        prm = _capi.QmapParams(k, mismatches, 1 if forward_only else 0, max_count, 0, (C.c_uint32 * 3)(0, 0, 0))
+        st = _capi.QmapStats()
+        _capi.check(self._L, self._L.dg_query_map(self._h, C.byref(prm), buf, off, len(recs), out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in _capi.QmapStats._fields_})
+        return [out[off[i]:off[i + 1]].copy() for i in range(len(recs))]
 
     def _map_runs(self, m, lo, hi):
         import numpy as np

@@ -18,6 +18,7 @@ DG_OPEN_BIG_TABLE = 8
 DG_Q_TOO_SHORT, DG_Q_DIST_ADJUSTED, DG_Q_MAX_MATCHES, DG_Q_NBHD_EXCEEDED = 1, 2, 4, 8
 DG_HUNT_COMPACT = 1
 DG_HUNT_PHASE_TIMES = 2
+DG_QMAP_INVALID = 0xFFFFFFFF
 
 
 class DgError(RuntimeError):
@@ -101,6 +102,17 @@ class MapMmStats(C.Structure):
                 ("early_exits", C.c_uint64), ("launches", C.c_uint64), ("ms_search", C.c_double)]
 
 
+class QmapParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("mismatches", C.c_uint32), ("forward_only", C.c_int32), ("max_count", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class QmapStats(C.Structure):
+    _fields_ = [("positions", C.c_uint64), ("valid", C.c_uint64), ("steps", C.c_uint64), ("table_reads", C.c_uint64),
+                ("verified_rows", C.c_uint64), ("early_exits", C.c_uint64), ("launches", C.c_uint64), ("ms_valid", C.c_double),
+                ("ms_search", C.c_double), ("ms_total", C.c_double)]
+
+
 class MinUniqueParams(C.Structure):
     _fields_ = [("max_k", C.c_uint32), ("forward_only", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -126,7 +138,7 @@ SYMBOLS = ["dg_index_open", "dg_index_close", "dg_index_stats", "dg_count", "dg_
            "dg_neighbors", "dg_buffer_free", "dg_hit_rows", "dg_hunt_rows", "dg_hunt_submit", "dg_hunt_wait", "dg_hunt_device_submit",
            "dg_chit_unpack", "dg_normalize_query", "dg_hunt_expand", "dg_index_stream", "dg_fm9_check",
            "dg_mappability", "dg_map_values", "dg_map_runs", "dg_map_device_values", "dg_map_stats", "dg_map_free",
-           "dg_mappability_mm", "dg_map_mm_stats", "dg_min_unique"]
+           "dg_mappability_mm", "dg_map_mm_stats", "dg_min_unique", "dg_query_map"]
 
 _lib = None
 
@@ -203,6 +215,7 @@ def load(path=None):
     L.dg_mappability_mm.argtypes = [vp, C.POINTER(MapMmParams), C.POINTER(vp)]
     L.dg_map_mm_stats.argtypes = [vp, C.POINTER(MapMmStats)]
     L.dg_min_unique.argtypes = [vp, C.POINTER(MinUniqueParams), C.POINTER(vp)]
+    L.dg_query_map.argtypes = [vp, C.POINTER(QmapParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapStats)]
     L.dg_map_free.restype = None
     if path is None:
         _lib = L

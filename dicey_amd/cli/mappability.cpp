@@ -3,9 +3,11 @@
 // starts there, on both strands, counted on the FM-index in HBM.  The device hands over runs of equal values per position chunk;
 // the host formats the chunks on several threads, compresses them (-o) into concatenated gzip members and writes them in order.
 // With -u the value is the minimum unique length instead (dg_min_unique): the shortest k-mer that starts at the position and is unique.
+// With -q the positions are those of the records of a second FASTA file, which need not be in the genome (dg_query_map): zero is a value there.
 #include <zlib.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cstdlib>
 #include <iostream>
 #include <thread>
@@ -19,10 +21,11 @@ namespace {
 
 const OptSpec kMapOpts[] = {{"help", '?', false},  {"genome", 'g', true},  {"kmer", 'k', true},
                             {"forward", 'f', false}, {"maxcount", 'c', true}, {"outfile", 'o', true},
-                            {"mismatches", 'e', true}, {"minunique", 'u', false}};
+                            {"mismatches", 'e', true}, {"minunique", 'u', false},
+                            {"query", 'q', true}};
 
 void map_usage() {
-  std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz" << std::endl;
+  std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz [-q targets.fa.gz]" << std::endl;
   std::cout << "Generic options:\n"
                "  -? [ --help ]                      show help message\n"
                "  -g [ --genome ] arg                genome file (indexed with dicey index: <genome stem>.fm9)\n"
@@ -31,6 +34,7 @@ void map_usage() {
                "  -f [ --forward ]                   forward strand only\n"
                "  -c [ --maxcount ] arg (=0)         write min(value, maxcount); 0 = exact values\n"
                "  -u [ --minunique ]                 write the minimum unique length instead; -k is then the largest length tried\n"
+               "  -q [ --query ] arg                 FASTA file of sequences to rate against the genome instead of the genome itself\n"
                "  -o [ --outfile ] arg               gzipped output file (default: plain text on stdout)\n"
                "\n"
                "Output: bedGraph lines name, start, end, value (0-based, end exclusive) of maximal runs of equal values, where the value\n"
@@ -42,6 +46,10 @@ void map_usage() {
                "With -u the value of a position is the smallest length k (at most -k, and inside the run of A/C/G/T that starts there) at\n"
                "which the k-mer that starts there has value 1: it occurs once and its reverse complement nowhere (-f: once on the forward\n"
                "strand).  Positions without such a length, still repeated at -k or at the end of their run, have no line.\n"
+               "With -q the lines are those of the records of the query file (upper-cased; the name is the header's first word), in file\n"
+               "order: the value of a position is the number of k-mers of the GENOME within -e mismatches of the record's k-mer and of its\n"
+               "reverse complement.  The sequences need not be in the genome, so 0 is a value (absent from the genome) and has lines of\n"
+               "its own; positions without a k-mer of A/C/G/T and records shorter than -k have no line.  -u cannot be combined with -q.\n"
                "\n";
 }
 
@@ -81,6 +89,102 @@ struct Piece {  // the runs of positions [a, b) of one sequence
   std::vector<uint32_t> len, value;
 };
 
+// the records of a FASTA file: the header's first word and the sequence, upper-cased (as `dicey index` does to the genome)
+bool read_fasta(const std::string& path, std::vector<std::string>& names, std::vector<std::string>& seqs) {
+  LineReader r(path);
+  if (!r.ok()) return false;
+  std::string line;
+  while (r.next(line)) {
+    if (!line.empty() && line[0] == '>') {
+      const size_t e = line.find_first_of(" \t\r", 1);
+      names.push_back(line.substr(1, e == std::string::npos ? std::string::npos : e - 1));
+      seqs.emplace_back();
+    } else if (!seqs.empty()) {
+      for (char c : line)
+        if (!(c == '\r' || c == ' ' || c == '\t')) seqs.back().push_back((char)std::toupper((unsigned char)c));
+    }
+  }
+  return !seqs.empty();
+}
+
+// bedGraph of the query records: one line per maximal run of equal values over valid positions, zero included
+int write_query_map(dg_index* ix, const dg_qmap_params& qp, const std::string& query, const std::string& outfile) {
+  std::vector<std::string> names, seqs;
+  if (!read_fasta(query, names, seqs)) return bail("Error: Could not read any sequence from " + query + "!");
+  std::vector<uint64_t> off(seqs.size() + 1, 0);
+  for (size_t i = 0; i < seqs.size(); ++i) off[i + 1] = off[i] + seqs[i].size();
+  std::string all;
+  all.reserve(off.back());
+  for (const std::string& s : seqs) all += s;
+  std::vector<uint32_t> val(off.back());
+  if (dg_query_map(ix, &qp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr) != DG_OK)
+    return bail(std::string("dicey: ") + dg_last_error());
+  FILE* fo = stdout;
+  if (!outfile.empty()) {
+    fo = std::fopen(outfile.c_str(), "wb");
+    if (!fo) return bail("Error: cannot open " + outfile + " for writing!");
+  }
+  const std::string dest = outfile.empty() ? std::string("stdout") : outfile;
+  bool ok = true, wrote = false;
+  std::string text, packed, err;
+  auto flush = [&]() {  // -o: one gzip member per flush, which gzip -dc reads in a row
+    if (text.empty() || !ok) return;
+    const std::string* w = &text;
+    if (!outfile.empty()) {
+      if (!gzip_member(text, packed)) {
+        err = "Error: compression failed!";
+        ok = false;
+        return;
+      }
+      w = &packed;
+    }
+    if (std::fwrite(w->data(), 1, w->size(), fo) != w->size()) {
+      err = "Error: short write to " + dest + "!";
+      ok = false;
+    }
+    wrote = true;
+    text.clear();
+  };
+  for (size_t i = 0; i < seqs.size() && ok; ++i) {
+    const uint32_t* v = val.data() + off[i];
+    const uint64_t len = seqs[i].size();
+    for (uint64_t a = 0; a < len;) {
+      uint64_t b = a + 1;
+      while (b < len && v[b] == v[a]) ++b;
+      if (v[a] != DG_QMAP_INVALID) {
+        text += names[i];
+        text.push_back('\t');
+        uint_append(text, a);
+        text.push_back('\t');
+        uint_append(text, b);
+        text.push_back('\t');
+        uint_append(text, v[a]);
+        text.push_back('\n');
+        if (text.size() >= (16u << 20)) flush();
+      }
+      a = b;
+    }
+  }
+  flush();
+  if (ok && !wrote && !outfile.empty()) {  // no run at all: still a valid (empty) gzip file
+    if (!gzip_member(std::string(), packed) || std::fwrite(packed.data(), 1, packed.size(), fo) != packed.size()) {
+      err = "Error: short write to " + dest + "!";
+      ok = false;
+    }
+  }
+  if (fo != stdout) {
+    if (std::fclose(fo) != 0 && ok) {
+      err = "Error: cannot finish writing " + outfile + "!";
+      ok = false;
+    }
+  } else if (std::fflush(stdout) != 0 && ok) {
+    err = "Error: short write to stdout!";
+    ok = false;
+  }
+  if (!ok) return bail(err);
+  return 0;
+}
+
 }  // namespace
 
 int mappability_main(int argc, char** argv) {
@@ -90,8 +194,8 @@ int mappability_main(int argc, char** argv) {
     map_usage();
     return -1;
   }
-  std::string genome, outfile;
-  bool help = false, have_genome = false, forward = false, minunique = false;
+  std::string genome, outfile, query;
+  bool help = false, have_genome = false, forward = false, minunique = false, have_query = false;
   long long k = 100, maxcount = 0, mismatches = 0;
   for (auto& kv : p.kv) {
     if (kv.first == "help") help = true;
@@ -102,6 +206,7 @@ int mappability_main(int argc, char** argv) {
     else if (kv.first == "outfile") outfile = kv.second;
     else if (kv.first == "mismatches") mismatches = std::strtoll(kv.second.c_str(), nullptr, 10);
     else if (kv.first == "minunique") minunique = true;
+    else if (kv.first == "query") { query = kv.second; have_query = true; }
   }
   if (help || !have_genome || !p.positional.empty()) {
     map_usage();
@@ -111,7 +216,9 @@ int mappability_main(int argc, char** argv) {
   if (mismatches < 0 || mismatches > 2) return bail("Error: number of mismatches " + std::to_string(mismatches) + " outside 0..2!");
   if (maxcount < 0 || maxcount > 0xFFFFFFFFll) return bail("Error: maxcount " + std::to_string(maxcount) + " outside 0..4294967295!");
   if (minunique && (mismatches != 0 || maxcount != 0)) return bail("Error: --minunique cannot be combined with --mismatches or --maxcount!");
+  if (minunique && have_query) return bail("Error: --minunique cannot be combined with --query!");
   if (!file_nonempty(genome)) return bail("Error: Genome does not exist!");
+  if (have_query && !file_nonempty(query)) return bail("Error: Query file " + query + " does not exist or is empty!");
   std::vector<uint32_t> seqlen;
   std::vector<std::string> seqname;
   if (!seq_len_name(genome, seqlen, seqname)) return bail("Error: Could not retrieve sequence lengths!");
@@ -132,6 +239,10 @@ int mappability_main(int argc, char** argv) {
   if (total != ist.n)
     return bail("Error: the sequence lengths of " + genome + " (" + std::to_string(total - 1) + " characters with separators) do not match the index " +
                 fm9 + " (" + std::to_string(ist.n - 1) + ")!");
+  if (have_query) {
+    const dg_qmap_params qp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, {0u, 0u, 0u}};
+    return write_query_map(ix, qp, query, outfile);
+  }
   dg_map_mm_params mp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, 0u};
   dg_min_unique_params up = {(uint32_t)k, forward ? 1 : 0, 0u, 0u};
   dg_map* m = nullptr;

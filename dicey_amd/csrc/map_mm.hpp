@@ -22,8 +22,11 @@ struct MmCounters {  // device record, one wave_add per field and wavefront
   unsigned long long heads, steps, table_reads, verified_rows, early_exits;
 };
 
-struct MmLane {  // one lane's search of one head: constants of the head and the running results
-  u64 p;         // text position of w
+struct MmLane {  // one lane's search of one k-mer w: its constants and the running results
+  const u8* pat;  // the buffer w is read from: the text for a group head, the query buffer for k_qmap (query_map.hpp).  8-byte reads of
+                  // it touch only the aligned words that overlap [p, p + k + 8): never in front of an 8-aligned buffer, and behind its
+                  // last k-mer inside the text's slack.  Windows are always read from f.text
+  u64 p;          // position of w in pat
   u32 k;
   bool rev;   // the pattern is revcomp(w)
   u32 W;      // intervals of at most W rows are verified on the text (0: never)
@@ -35,7 +38,7 @@ struct MmLane {  // one lane's search of one head: constants of the head and the
 // the pattern's character met at backward-search step t (its LAST character at t = 0), as a code 0..3.  revcomp(w) from its last
 // character to its first is w from its first to its last, complemented.
 DG_DEV u32 mm_pat_code(const FmView& f, const MmLane& c, u32 t) {
-  const u32 b = f.text[c.rev ? c.p + t : c.p + c.k - 1 - t];
+  const u32 b = c.pat[c.rev ? c.p + t : c.p + c.k - 1 - t];
   const u32 x = acgt_code(b);
   return c.rev ? 3u - x : x;
 }
@@ -56,12 +59,12 @@ DG_DEV u64 mm_complement_bytes(u64 x) {
 
 // the first m characters of the pattern from index j on, eight per word (byte i = pattern[j + i]); bytes at or behind m are undefined
 DG_DEV u64 mm_pat8(const FmView& f, const MmLane& c, u32 m, u32 j) {
-  if (!c.rev) return text8(f.text, c.p + j);
+  if (!c.rev) return text8(c.pat, c.p + j);
   // pattern[i] = complement of w[k - 1 - i]: the eight bytes that end at w[k - 1 - j], reversed; near the pattern's end the word is
   // read from w[k - m] on (never in front of w) and shifted
   const u32 rem = m - j;
-  if (rem >= 8) return mm_complement_bytes(__builtin_bswap64(text8(f.text, c.p + c.k - 8 - j)));
-  return mm_complement_bytes(__builtin_bswap64(text8(f.text, c.p + c.k - m)) >> (8 * (8 - rem)));
+  if (rem >= 8) return mm_complement_bytes(__builtin_bswap64(text8(c.pat, c.p + c.k - 8 - j)));
+  return mm_complement_bytes(__builtin_bswap64(text8(c.pat, c.p + c.k - m)) >> (8 * (8 - rem)));
 }
 
 // rows [lo, hi) hold the suffixes that start with the t characters consumed so far: count those whose k - t characters in front spell
@@ -166,6 +169,7 @@ __global__ void __launch_bounds__(256) k_heads_mm(FmView f, u32 k, int forward_o
                                                  MmCounters* ctr) {
   const u64 i = r0 + (u64)blockIdx.x * blockDim.x + threadIdx.x;
   MmLane c;
+  c.pat = f.text;
   c.p = 0;
   c.k = k;
   c.rev = false;

@@ -41,6 +41,7 @@ extern "C" {
  * 6: dg_hunt_result grows by stream / d_block / d_block_bytes (the gather over RCCL lives in libdiceygather.so, include/dicey_gather.h)
  * 7 (additive exports, same version): dg_mappability, dg_map_values, dg_map_runs, dg_map_device_values, dg_map_stats, dg_map_free
  * 7 (additive exports, same version): dg_mappability_mm, dg_map_mm_stats ((k,e)-mappability, up to two mismatches)
+ * 7 (additive exports, same version): dg_query_map (the same counts for the k-mers of sequences outside the index)
  * 7 (additive exports, same version): dg_min_unique (the shortest unique k-mer at each position) */
 #define DG_ABI_VERSION 7
 
@@ -530,6 +531,47 @@ typedef struct {
   uint32_t reserved;    /* 0 */
 } dg_min_unique_params;
 int dg_min_unique(dg_index* ix, const dg_min_unique_params* p, dg_map** out);
+
+/* ABI 7, additive.  Query mappability: the (k,e) counts of dg_mappability_mm for the k-mers of sequences that are NOT in the index (a
+ * transcript across an exon-exon junction, a transgene, a viral genome, another allele).  Record i is seqs[off[i] .. off[i+1]), bytes
+ * as given; empty records are allowed; values[off[i] + p] answers position p of record i.  For a record Q, a position p and e =
+ * mismatches in 0..2:
+ *   p is VALID when p + k <= len(Q) and w = Q[p, p+k) holds only A/C/G/T (case-sensitive, the rule of the text),
+ *   fwd_e(p) = #{valid windows q of the TEXT : Hamming(T[q, q+k), w) <= e},   rev_e(p) = the same against revcomp(w),
+ *   value(p) = fwd_e(p) + rev_e(p)   (forward_only: fwd_e(p)).
+ * The windows are those dg_mappability_mm counts: A/C/G/T only, inside one sequence, never across '\n', an N or an IUPAC letter, never
+ * starting before position 0.  At e = 0 the value is sdsl::count(w) + sdsl::count(revcomp(w)).  Unlike the genome track w itself is
+ * in the count only when the genome holds it, so 0 IS A VALUE (absent from the genome) and invalid positions carry DG_QMAP_INVALID
+ * instead; sums saturate at 0xFFFFFFFE; max_count = C > 0 writes min(value, C) (invalid stays invalid) and the search of a k-mer
+ * stops once its total reaches C.  The computation runs on the handle's stream, positions in chunks of launches, and needs the query
+ * bytes, 4 bytes per position and two bitmaps of free HBM (DG_ENOMEM before any kernel otherwise).  nseq = 0 succeeds and writes
+ * nothing.  Checked in this order, the parameter block before the handle: a null parameter block, non-zero flags or reserved
+ * DG_EINVAL; k outside 10..1000 or mismatches > 2 DG_ELIMIT; off[nseq] + nseq >= 2^31 DG_ELIMIT; a null handle, null seqs / off /
+ * values (where there is something to read or write) or decreasing offsets DG_EINVAL; then DG_EINVAL while a dg_hunt_submit batch is in
+ * flight on the handle.  On every failure `values` is left untouched. */
+#define DG_QMAP_INVALID 0xFFFFFFFFu
+typedef struct {
+  uint32_t k;           /* k-mer length, 10..1000 */
+  uint32_t mismatches;  /* e: 0, 1 or 2 substitutions */
+  int32_t forward_only; /* fwd_e only */
+  uint32_t max_count;   /* 0 = exact values, else min(value, max_count) */
+  uint32_t flags;       /* 0 */
+  uint32_t reserved[3]; /* 0 */
+} dg_qmap_params;
+typedef struct {
+  uint64_t positions;     /* off[nseq] - off[0]: values written */
+  uint64_t valid;         /* positions with a k-mer of A/C/G/T (the others hold DG_QMAP_INVALID) */
+  uint64_t steps;         /* backward-search steps (one pair of Occ lines each, all four characters) */
+  uint64_t table_reads;   /* K-mer table entries read */
+  uint64_t verified_rows; /* suffix-array rows finished on the text */
+  uint64_t early_exits;   /* k-mers whose search stopped at max_count */
+  uint64_t launches;      /* kernel launches of the search (positions go through in chunks) */
+  double ms_valid;        /* device time: upload of the queries and the valid-position bitmap */
+  double ms_search;       /* device time of the search */
+  double ms_total;        /* ms_valid + ms_search */
+} dg_qmap_stats_t;
+int dg_query_map(dg_index* ix, const dg_qmap_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
+                 dg_qmap_stats_t* stats /* may be NULL */);
 
 const char* dg_last_error(void);
 int dg_abi_version(void);

@@ -6,7 +6,11 @@ forward only; with --mismatches 1|2 the runs go through dg_mappability_mm ((k,e)
 dg_map_mm_stats per head.  With --min-unique [--maxk K] the runs go through dg_min_unique instead (the shortest unique k-mer per
 position): total, forward (neighbour prefixes) and reverse (the other strand's walk) ms, walk steps per position and, from the library's
 DICEY_TIMING line, the longest launch of the walk — and beside each, on the same genome and build, ONE exact dg_mappability pass at
-k = K: a bisection over 10..1000 needs seven of those.  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
+k = K: a bisection over 10..1000 needs seven of those.  With --query the runs go through dg_query_map (k-mer counts for sequences
+outside the index): one query set of 1 Mb cut from the genome with 1 % substitutions plus 1 Mb random, in records of 10 kb, at e = 0, 1, 2
+per k, positions/s from the call's wall time and from the device time, the search counters per valid position, the longest launch — and,
+at e = 0 in the same run, the route a build without dg_query_map offers to the same numbers: dg_count on every k-mer and its reverse
+complement (cut out on the host, uploaded k-fold).  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
 Prints one JSON line."""
 import argparse, ctypes as C, json, os, re, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,6 +27,8 @@ ap.add_argument("--ks", default="24,36,50,100,150")
 ap.add_argument("--mismatches", type=int, default=0, help="e of (k,e)-mappability: 0 (exact), 1 or 2")
 ap.add_argument("--min-unique", action="store_true", help="time dg_min_unique (max_k = --maxk) beside one exact pass at k = --maxk")
 ap.add_argument("--maxk", type=int, default=100, help="max_k of --min-unique")
+ap.add_argument("--query", action="store_true", help="time dg_query_map on a 2 Mb query set (per k of --ks, e = 0, 1, 2) beside dg_count on its k-mers")
+ap.add_argument("--query-mb", type=float, default=1.0, help="Mb of each half of the --query set (cut from the genome / random)")
 ap.add_argument("--maxcount", type=int, default=0, help="max_count of the runs (0 = exact values)")
 ap.add_argument("--forward", choices=["both", "no", "yes"], default="both", help="which strand settings to time")
 ap.add_argument("--keep-index", action="store_true", help="leave the generated index (and its .lens.json) in --workdir for --fm9 runs")
@@ -97,7 +103,80 @@ def min_unique_run(fo):
             "cost_in_exact_passes": round(st.ms_total / max(xs.ms_total, 1e-9), 2)}
 
 
-if a.min_unique:
+def query_set():
+    """records of 10 kb: --query-mb Mb cut from the genome (pieces of 100 kb from seeded places) with 1 % substitutions, then as much random"""
+    import numpy as np
+    rng = np.random.default_rng(11)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    half = int(a.query_mb * 1e6)
+    piece = min(10_000, half)
+    starts = [int(x) for x in rng.integers(0, n - 1 - piece, half // piece)]
+    cut = np.frombuffer(b"".join(ix.extract([(p, p + piece - 1) for p in starts])), dtype=np.uint8).copy()
+    hits = rng.integers(0, len(cut), len(cut) // 100)
+    ok = np.isin(cut[hits], acgt)  # an N or a sequence end inside a piece stays what it is
+    cut[hits[ok]] = acgt[rng.integers(0, 4, int(ok.sum()))]
+    both = np.concatenate([cut, acgt[rng.integers(0, 4, half)]])
+    return [both[i:i + 10_000].tobytes() for i in range(0, len(both), 10_000)]
+
+
+def query_runs(k, recs):
+    import numpy as np
+    buf = b"".join(recs)
+    off = np.zeros(len(recs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(r) for r in recs])
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    vals = {}
+    for e in (0, 1, 2):
+        out_v = np.zeros(len(buf), dtype=np.uint32)
+        prm = _capi.QmapParams(k, e, 0, a.maxcount, 0, (C.c_uint32 * 3)(0, 0, 0))
+        st = _capi.QmapStats()
+        _capi.check(L, L.dg_query_map(ix.handle, C.byref(prm), buf, off.ctypes.data_as(u64p), 1, out_v.ctypes.data_as(u32p), None))  # (warm-up: one record)
+        os.environ["DICEY_TIMING"] = "1"
+        t0 = time.time()
+        err = stderr_of(lambda: _capi.check(L, L.dg_query_map(ix.handle, C.byref(prm), buf, off.ctypes.data_as(u64p), len(recs),
+                                                                out_v.ctypes.data_as(u32p), C.byref(st))))
+        wall = time.time() - t0
+        del os.environ["DICEY_TIMING"]
+        line = re.search(r"query map e=\d+: (\d+) launches of the search, [0-9.]+ ms in all, longest ([0-9.]+) ms", err)
+        v = max(st.valid, 1)
+        vals[e] = out_v
+        runs.append({"query": True, "k": k, "mismatches": e, "max_count": a.maxcount, "positions": st.positions, "valid": st.valid,
+                     "absent": int((out_v == 0).sum()), "wall_s": round(wall, 4), "ms_total": round(st.ms_total, 2), "ms_valid": round(st.ms_valid, 2),
+                     "ms_search": round(st.ms_search, 2), "positions_per_s_wall": round(st.valid / wall), "positions_per_s_device": round(st.valid / max(st.ms_total, 1e-9) * 1e3),
+                     "launches": st.launches, "longest_launch_ms": float(line.group(2)) if line else None, "early_exits": st.early_exits,
+                     "steps_per_position": round(st.steps / v, 2), "table_reads_per_position": round(st.table_reads / v, 2),
+                     "verified_rows_per_position": round(st.verified_rows / v, 2)})
+        print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+    # the other route to the e = 0 numbers: every valid k-mer and its reverse complement through dg_count
+    t0 = time.time()
+    b = np.frombuffer(buf, dtype=np.uint8)
+    pos = np.nonzero(vals[0] != _capi.DG_QMAP_INVALID)[0]
+    win = np.lib.stride_tricks.sliding_window_view(b, k)[pos]
+    comp = np.arange(256, dtype=np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    pats = np.empty((len(pos), 2, k), dtype=np.uint8)
+    pats[:, 0] = win
+    pats[:, 1] = comp[win][:, ::-1]
+    pbuf = pats.tobytes()
+    poff = np.arange(0, 2 * len(pos) * k + 1, k, dtype=np.uint64)
+    cut_s = time.time() - t0
+    cnt = np.zeros(2 * len(pos), dtype=np.uint64)
+    _capi.check(L, L.dg_count(ix.handle, pbuf, poff.ctypes.data_as(u64p), 1000, cnt.ctypes.data_as(u64p)))  # (warm-up: workspaces)
+    t0 = time.time()
+    _capi.check(L, L.dg_count(ix.handle, pbuf, poff.ctypes.data_as(u64p), 2 * len(pos), cnt.ctypes.data_as(u64p)))
+    wall = time.time() - t0
+    same = bool((cnt.reshape(-1, 2).sum(axis=1) == vals[0][pos]).all()) if a.maxcount == 0 else None
+    runs.append({"query": True, "route": "dg_count per k-mer", "k": k, "mismatches": 0, "patterns": 2 * len(pos), "upload_mb": round(len(pbuf) / 1e6, 1),
+                 "host_cut_s": round(cut_s, 3), "wall_s": round(wall, 4), "positions_per_s_wall": round(len(pos) / wall), "same_values": same})
+    print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+
+
+if a.query:
+    recs = query_set()
+    for k in [int(x) for x in a.ks.split(",")]:
+        query_runs(k, recs)
+    ks = []
+elif a.min_unique:
     for fo in STRANDS:
         runs.append(min_unique_run(fo))
         print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
@@ -140,7 +219,7 @@ ix.close()
 # the CLI end to end: open + map + runs + format + gzip
 stem = os.path.join(a.workdir, "dicey_map_bench_cli_%s" % a.genome)
 gz = stem + ".bedgraph.gz"
-if a.cli_k and not a.min_unique:
+if a.cli_k and not a.min_unique and not a.query:
     with open(stem + ".fa", "w") as f:
         f.write(">chr1\nN\n")
     with open(stem + ".fa.fai", "w") as f:
