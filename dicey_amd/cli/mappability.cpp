@@ -4,6 +4,7 @@
 // the host formats the chunks on several threads, compresses them (-o) into concatenated gzip members and writes them in order.
 // With -u the value is the minimum unique length instead (dg_min_unique): the shortest k-mer that starts at the position and is unique.
 // With -q the positions are those of the records of a second FASTA file, which need not be in the genome (dg_query_map): zero is a value there.
+// With -q -l the value is the query minimum length (dg_query_min_len): the shortest k-mer from the position with at most -t places in the genome.
 #include <zlib.h>
 
 #include <algorithm>
@@ -22,7 +23,8 @@ namespace {
 const OptSpec kMapOpts[] = {{"help", '?', false},  {"genome", 'g', true},  {"kmer", 'k', true},
                             {"forward", 'f', false}, {"maxcount", 'c', true}, {"outfile", 'o', true},
                             {"mismatches", 'e', true}, {"minunique", 'u', false},
-                            {"query", 'q', true}};
+                            {"query", 'q', true}, {"minlength", 'l', false}, {"shortest", 's', true},
+                            {"atmost", 't', true}};
 
 void map_usage() {
   std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz [-q targets.fa.gz]" << std::endl;
@@ -35,6 +37,9 @@ void map_usage() {
                "  -c [ --maxcount ] arg (=0)         write min(value, maxcount); 0 = exact values\n"
                "  -u [ --minunique ]                 write the minimum unique length instead; -k is then the largest length tried\n"
                "  -q [ --query ] arg                 FASTA file of sequences to rate against the genome instead of the genome itself\n"
+               "  -l [ --minlength ]                 with -q: write the shortest specific length instead; -k is then the largest length tried\n"
+               "  -s [ --shortest ] arg (=10)        with -l: the smallest length tried (10..1000, at most -k)\n"
+               "  -t [ --atmost ] arg (=0)           with -l: a length is specific when its k-mer has at most this many places in the genome\n"
                "  -o [ --outfile ] arg               gzipped output file (default: plain text on stdout)\n"
                "\n"
                "Output: bedGraph lines name, start, end, value (0-based, end exclusive) of maximal runs of equal values, where the value\n"
@@ -50,6 +55,10 @@ void map_usage() {
                "order: the value of a position is the number of k-mers of the GENOME within -e mismatches of the record's k-mer and of its\n"
                "reverse complement.  The sequences need not be in the genome, so 0 is a value (absent from the genome) and has lines of\n"
                "its own; positions without a k-mer of A/C/G/T and records shorter than -k have no line.  -u cannot be combined with -q.\n"
+               "With -q -l the value of a position of a record is the smallest length k (from -s to -k, inside the run of A/C/G/T that starts\n"
+               "there) at which the genome holds at most -t k-mers within -e mismatches of the record's k-mer and of its reverse complement\n"
+               "(-f: of the k-mer alone): -t 0 asks how long an oligo must be to have no place in the genome, -t 1 for at most one place.\n"
+               "Positions without such a length, and positions where not even a k-mer of length -s starts, have no line.\n"
                "\n";
 }
 
@@ -107,8 +116,9 @@ bool read_fasta(const std::string& path, std::vector<std::string>& names, std::v
   return !seqs.empty();
 }
 
-// bedGraph of the query records: one line per maximal run of equal values over valid positions, zero included
-int write_query_map(dg_index* ix, const dg_qmap_params& qp, const std::string& query, const std::string& outfile) {
+// bedGraph of the query records: one line per maximal run of equal values over valid positions, zero included.  With lp (-l) the values
+// are minimum lengths and zero, no length, has no line either
+int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_params* lp, const std::string& query, const std::string& outfile) {
   std::vector<std::string> names, seqs;
   if (!read_fasta(query, names, seqs)) return bail("Error: Could not read any sequence from " + query + "!");
   std::vector<uint64_t> off(seqs.size() + 1, 0);
@@ -117,8 +127,9 @@ int write_query_map(dg_index* ix, const dg_qmap_params& qp, const std::string& q
   all.reserve(off.back());
   for (const std::string& s : seqs) all += s;
   std::vector<uint32_t> val(off.back());
-  if (dg_query_map(ix, &qp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr) != DG_OK)
-    return bail(std::string("dicey: ") + dg_last_error());
+  const int rc = lp ? dg_query_min_len(ix, lp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
+                    : dg_query_map(ix, &qp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr);
+  if (rc != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
   FILE* fo = stdout;
   if (!outfile.empty()) {
     fo = std::fopen(outfile.c_str(), "wb");
@@ -151,7 +162,7 @@ int write_query_map(dg_index* ix, const dg_qmap_params& qp, const std::string& q
     for (uint64_t a = 0; a < len;) {
       uint64_t b = a + 1;
       while (b < len && v[b] == v[a]) ++b;
-      if (v[a] != DG_QMAP_INVALID) {
+      if (v[a] != DG_QMAP_INVALID && !(lp && v[a] == 0)) {
         text += names[i];
         text.push_back('\t');
         uint_append(text, a);
@@ -195,8 +206,9 @@ int mappability_main(int argc, char** argv) {
     return -1;
   }
   std::string genome, outfile, query;
-  bool help = false, have_genome = false, forward = false, minunique = false, have_query = false;
-  long long k = 100, maxcount = 0, mismatches = 0;
+  bool help = false, have_genome = false, forward = false, minunique = false, have_query = false, minlength = false, have_shortest = false,
+       have_atmost = false;
+  long long k = 100, maxcount = 0, mismatches = 0, shortest = 10, atmost = 0;
   for (auto& kv : p.kv) {
     if (kv.first == "help") help = true;
     else if (kv.first == "genome") { genome = kv.second; have_genome = true; }
@@ -207,6 +219,9 @@ int mappability_main(int argc, char** argv) {
     else if (kv.first == "mismatches") mismatches = std::strtoll(kv.second.c_str(), nullptr, 10);
     else if (kv.first == "minunique") minunique = true;
     else if (kv.first == "query") { query = kv.second; have_query = true; }
+    else if (kv.first == "minlength") minlength = true;
+    else if (kv.first == "shortest") { shortest = std::strtoll(kv.second.c_str(), nullptr, 10); have_shortest = true; }
+    else if (kv.first == "atmost") { atmost = std::strtoll(kv.second.c_str(), nullptr, 10); have_atmost = true; }
   }
   if (help || !have_genome || !p.positional.empty()) {
     map_usage();
@@ -217,6 +232,12 @@ int mappability_main(int argc, char** argv) {
   if (maxcount < 0 || maxcount > 0xFFFFFFFFll) return bail("Error: maxcount " + std::to_string(maxcount) + " outside 0..4294967295!");
   if (minunique && (mismatches != 0 || maxcount != 0)) return bail("Error: --minunique cannot be combined with --mismatches or --maxcount!");
   if (minunique && have_query) return bail("Error: --minunique cannot be combined with --query!");
+  if (minlength && !have_query) return bail("Error: --minlength needs --query!");
+  if (minlength && maxcount != 0) return bail("Error: --minlength cannot be combined with --maxcount!");
+  if ((have_shortest || have_atmost) && !minlength) return bail("Error: --shortest and --atmost need --minlength!");
+  if (shortest < 10 || shortest > 1000) return bail("Error: shortest length " + std::to_string(shortest) + " outside 10..1000!");
+  if (shortest > k) return bail("Error: shortest length " + std::to_string(shortest) + " above the largest length " + std::to_string(k) + " (-k)!");
+  if (atmost < 0 || atmost > 0xFFFFFFFDll) return bail("Error: atmost " + std::to_string(atmost) + " outside 0..4294967293!");
   if (!file_nonempty(genome)) return bail("Error: Genome does not exist!");
   if (have_query && !file_nonempty(query)) return bail("Error: Query file " + query + " does not exist or is empty!");
   std::vector<uint32_t> seqlen;
@@ -241,7 +262,8 @@ int mappability_main(int argc, char** argv) {
                 fm9 + " (" + std::to_string(ist.n - 1) + ")!");
   if (have_query) {
     const dg_qmap_params qp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, {0u, 0u, 0u}};
-    return write_query_map(ix, qp, query, outfile);
+    const dg_qminlen_params lp = {(uint32_t)shortest, (uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)atmost, 0u, {0u, 0u}};
+    return write_query_map(ix, qp, minlength ? &lp : nullptr, query, outfile);
   }
   dg_map_mm_params mp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, 0u};
   dg_min_unique_params up = {(uint32_t)k, forward ? 1 : 0, 0u, 0u};

@@ -16,7 +16,8 @@
 // dg_min_unique (min_unique.hpp) answers the inverse question on the same handle type: per position the smallest k at which the value
 // is 1, from one pass over neighbouring suffixes and one backward search per rank.
 // dg_query_map (query_map.hpp) runs phase 1 on a buffer of query records laid out like the text and then one search per valid position
-// of it: the (k,e) counts of k-mers that are not in the index.
+// of it: the (k,e) counts of k-mers that are not in the index.  dg_query_min_len (query_min_len.hpp) looks, on the same buffer, for the
+// smallest k at which that count is at most t.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -206,6 +207,7 @@ __global__ void __launch_bounds__(256) k_heads(FmView f, u32 k, int forward_only
 }  // namespace dg
 #include "map_mm.hpp"  // k_heads' sibling for e >= 1 mismatches
 #include "query_map.hpp"  // the same search per position of a query buffer (dg_query_map)
+#include "query_min_len.hpp"  // and the search for the smallest specific k per position (dg_query_min_len)
 namespace dg {
 
 // out[SA[i]] = the total of i's group (heads hold it in their own slot; members hold their head's rank), 0 for invalid ranks
@@ -483,6 +485,126 @@ static int min_unique_impl(dg_index* ix, u32 max_k, int forward_only, dg_map* m)
 
 // default positions per k_qmap launch (the same reasoning as MM_HEAD_CHUNK; DESIGN.md §10 has the measurement)
 static constexpr u64 QMAP_CHUNK = 1ULL << 20;
+// default positions per k_qminlen launch: a lane does several probes one after the other (DESIGN.md §10 has the measurement)
+static constexpr u64 QMINLEN_CHUNK = 1ULL << 18;
+
+// the records as REC1 '\n' REC2 '\n' ...: record i at off[i] - off[0] + i, a '\n' behind each
+static std::vector<u8> query_pack(const uint8_t* seqs, const uint64_t* off, size_t nseq) {
+  const u64 base = off[0];
+  std::vector<u8> hq(off[nseq] - base + nseq);
+  for (size_t i = 0; i < nseq; ++i) {
+    const u64 len = off[i + 1] - off[i];
+    if (len) std::memcpy(&hq[off[i] - base + i], seqs + off[i], len);
+    hq[off[i + 1] - base + i] = '\n';
+  }
+  return hq;
+}
+// and the values of the buffer's positions back in the caller's layout (the '\n' positions dropped)
+static void query_unpack(const std::vector<u32>& vals, const uint64_t* off, size_t nseq, uint32_t* values) {
+  const u64 base = off[0];
+  for (size_t i = 0; i < nseq; ++i) {
+    const u64 len = off[i + 1] - off[i];
+    if (len) std::memcpy(values + off[i], &vals[off[i] - base + i], len * 4);
+  }
+}
+
+// the checks dg_query_map and dg_query_min_len share behind their parameter block: the size limit, then the handle and the pointers.
+// need_device: a process without a HIP device is told so (DG_ENODEV) before the handle it cannot have is looked at
+static int query_args_check(const char* who, dg_index* ix, const uint8_t* seqs, const uint64_t* off, size_t nseq, const uint32_t* values,
+                            bool need_device) {
+  const u64 total = (off && nseq) ? off[nseq] : 0;
+  if (total >= (1ULL << 31) || (u64)nseq >= (1ULL << 31) || total + nseq >= (1ULL << 31))
+    return fail(DG_ELIMIT, "%s: %llu query bytes in %llu records: 2^31 or more with their separators", who, (unsigned long long)total,
+                (unsigned long long)nseq);
+  if (need_device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(DG_ENODEV, "%s: no HIP device available", who);
+  }
+  if (!ix || (nseq && !off) || (total && (!seqs || !values))) return fail(DG_EINVAL, "%s: null argument", who);
+  for (size_t i = 0; i < nseq; ++i)
+    if (off[i] > off[i + 1]) return fail(DG_EINVAL, "%s: offsets decrease at record %llu", who, (unsigned long long)i);
+  if (ix->view.n < 2 || ix->view.n > 0xFFFFFFFFull) return fail(DG_ELIMIT, "%s: index of %llu suffixes", who, (unsigned long long)ix->view.n);
+  if (any_lane_busy(ix)) return fail(DG_EINVAL, "%s: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)", who);
+  return DG_OK;
+}
+
+// The device side of a query buffer: the bytes in whole 64-byte blocks with the text's slack behind, one u32 per position, `nbm` bitmaps
+// of nw words each (the A/C/G/T bitmap first) and a counter record.  alloc() checks the free memory and allocates everything; upload()
+// queues the copy and k_acgt_bits.
+struct QueryDev {
+  hipStream_t st;
+  u64 qn = 0, nw_data = 0, nw = 0, q_bytes = 0;
+  void *q = nullptr, *out = nullptr, *bm = nullptr, *ctr = nullptr;
+  explicit QueryDev(hipStream_t s) : st(s) {}
+  ~QueryDev() {
+    (void)hipStreamSynchronize(st);
+    if (q) big_free(q, st);
+    if (out) big_free(out, st);
+    if (bm) big_free(bm, st);
+    if (ctr) (void)hipFree(ctr);
+    (void)hipStreamSynchronize(st);
+  }
+  // k: the longest k-mer looked at, which sizes the zero words behind the bitmap's data
+  int alloc(const char* who, u64 qn_, u32 k, u32 nbm, size_t ctr_bytes) {
+    qn = qn_;
+    nw_data = (qn + 63) / 64;
+    nw = nw_data + (k + 63) / 64 + 4;
+    const size_t bm_bytes = nw * 8;
+    q_bytes = nw_data * 64 + 64;  // whole 64-byte blocks for k_acgt_bits, then the text's slack
+    const u64 need = q_bytes + qn * 4 + 256 + nbm * bm_bytes + 64;
+    size_t free_b = 0, total_b = 0;
+    DG_HIP(hipMemGetInfo(&free_b, &total_b));
+    if ((u64)free_b < need + (64ULL << 20))
+      return fail(DG_ENOMEM, "%s: needs %llu MB of device memory, %llu MB free", who, (unsigned long long)(need >> 20),
+                  (unsigned long long)(free_b >> 20));
+    DG_HIP(big_alloc(&q, q_bytes, st));
+    DG_HIP(big_alloc(&out, qn * 4 + 256, st));
+    DG_HIP(big_alloc(&bm, nbm * bm_bytes, st));
+    DG_HIP(hipMalloc(&ctr, ctr_bytes));
+    return DG_OK;
+  }
+  u64* acgt() const { return (u64*)bm; }
+  int upload(const std::vector<u8>& hq) {
+    DG_HIP(hipMemsetAsync((u8*)q + (qn & ~63ULL), 0, q_bytes - (qn & ~63ULL), st));  // the tail of the last block and the slack
+    DG_HIP(hipMemcpyAsync(q, hq.data(), qn, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_acgt_bits, dim3(ceil_div(nw, 256)), dim3(256), 0, st, (const u8*)q, qn, acgt(), nw);
+    return DG_OK;
+  }
+};
+
+// the events of a chunked search: upload | search, and with DICEY_TIMING one per launch, for the longest one
+struct ChunkTimer {
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  std::vector<hipEvent_t> lev;
+  const bool timing = std::getenv("DICEY_TIMING") != nullptr;
+  ~ChunkTimer() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : lev) (void)hipEventDestroy(e);
+  }
+  int init() {
+    for (auto& e : ev) DG_HIP(hipEventCreate(&e));
+    return DG_OK;
+  }
+  int launch(hipStream_t st) {  // in front of every launch of the search
+    if (!timing) return DG_OK;
+    hipEvent_t e;
+    DG_HIP(hipEventCreate(&e));
+    lev.push_back(e);
+    DG_HIP(hipEventRecord(e, st));
+    return DG_OK;
+  }
+  int read(float ms[2], float* longest) {  // once the stream has been synchronised
+    for (int j = 0; j < 2; ++j) DG_HIP(hipEventElapsedTime(&ms[j], ev[j], ev[j + 1]));
+    *longest = 0;
+    for (size_t j = 0; j < lev.size(); ++j) {
+      float t = 0;
+      DG_HIP(hipEventElapsedTime(&t, lev[j], j + 1 < lev.size() ? lev[j + 1] : ev[2]));
+      *longest = std::max(*longest, t);
+    }
+    return DG_OK;
+  }
+};
 
 // hq: the records as REC1 '\n' REC2 '\n' ... (qn bytes); vals: u32[qn], one value per buffer position
 static int query_map_impl(dg_index* ix, const dg_qmap_params* prm, const std::vector<u8>& hq, std::vector<u32>& vals, dg_qmap_stats_t* stt) {
@@ -490,74 +612,30 @@ static int query_map_impl(dg_index* ix, const dg_qmap_params* prm, const std::ve
   const u64 qn = hq.size();
   const u32 k = prm->k;
   hipStream_t st = ix->stream;
-  const u64 nw_data = (qn + 63) / 64, nw = nw_data + (k + 63) / 64 + 4;
-  const size_t bm_bytes = nw * 8;
-  const u64 q_bytes = nw_data * 64 + 64;  // whole 64-byte blocks for k_acgt_bits, then the text's slack
-  const u64 need = q_bytes + qn * 4 + 256 + 2 * bm_bytes + 64;
-  size_t free_b = 0, total_b = 0;
-  DG_HIP(hipMemGetInfo(&free_b, &total_b));
-  if ((u64)free_b < need + (64ULL << 20))
-    return fail(DG_ENOMEM, "dg_query_map: needs %llu MB of device memory, %llu MB free", (unsigned long long)(need >> 20),
-                (unsigned long long)(free_b >> 20));
-  struct Bufs {
-    hipStream_t st;
-    void *q = nullptr, *out = nullptr, *bm = nullptr, *ctr = nullptr;
-    ~Bufs() {
-      (void)hipStreamSynchronize(st);
-      if (q) big_free(q, st);
-      if (out) big_free(out, st);
-      if (bm) big_free(bm, st);
-      if (ctr) (void)hipFree(ctr);
-      (void)hipStreamSynchronize(st);
-    }
-  } b{st};
-  DG_HIP(big_alloc(&b.q, q_bytes, st));
-  DG_HIP(big_alloc(&b.out, qn * 4 + 256, st));
-  DG_HIP(big_alloc(&b.bm, 2 * bm_bytes, st));
-  DG_HIP(hipMalloc(&b.ctr, sizeof(QmapCounters)));
+  QueryDev b(st);
+  DG_TRY(b.alloc("dg_query_map", qn, k, 2, sizeof(QmapCounters)));
   u64 chunk = QMAP_CHUNK;
   u32 W = MM_NARROW;
   if (const char* e = exp_env("DICEY_QMAP_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
   if (const char* e = exp_env("DICEY_MAP_NARROW")) W = (u32)std::min<u64>(std::strtoull(e, nullptr, 10), 0xFFFFFFFFull);
-  const bool timing = std::getenv("DICEY_TIMING") != nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  struct Evs {
-    hipEvent_t* e;
-    ~Evs() {
-      for (int j = 0; j < 3; ++j)
-        if (e[j]) (void)hipEventDestroy(e[j]);
-    }
-  } evs{ev};
-  for (auto& e : ev) DG_HIP(hipEventCreate(&e));
-  std::vector<hipEvent_t> lev;  // DICEY_TIMING: one event per launch, for the longest one
-  struct LaunchEvs {
-    std::vector<hipEvent_t>& v;
-    ~LaunchEvs() {
-      for (hipEvent_t e : v) (void)hipEventDestroy(e);
-    }
-  } levs{lev};
+  ChunkTimer tm;
+  DG_TRY(tm.init());
   const u8* q = (const u8*)b.q;
-  u64* acgt = (u64*)b.bm;
+  const u64 nw = b.nw, nw_data = b.nw_data;
+  u64* acgt = b.acgt();
   u64* valid = acgt + nw;
   QmapCounters* ctr = (QmapCounters*)b.ctr;
   const u32 TB = 256;
   DG_HIP(hipMemsetAsync(b.ctr, 0, sizeof(QmapCounters), st));
-  DG_HIP(hipEventRecord(ev[0], st));
-  DG_HIP(hipMemsetAsync((u8*)b.q + (qn & ~63ULL), 0, q_bytes - (qn & ~63ULL), st));  // the tail of the last block and the slack
-  DG_HIP(hipMemcpyAsync(b.q, hq.data(), qn, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_acgt_bits, dim3(ceil_div(nw, TB)), dim3(TB), 0, st, q, qn, acgt, nw);
+  DG_HIP(hipEventRecord(tm.ev[0], st));
+  DG_TRY(b.upload(hq));
   DG_HIP(hipMemsetAsync(valid + nw_data, 0, (nw - nw_data) * 8, st));
   hipLaunchKernelGGL(k_valid_bits, dim3(ceil_div(nw_data, TB)), dim3(TB), 0, st, (const u64*)acgt, nw_data, k, valid);
-  DG_HIP(hipEventRecord(ev[1], st));
+  DG_HIP(hipEventRecord(tm.ev[1], st));
   u64 launches = 0;
   for (u64 p0 = 0; p0 < qn; p0 += chunk, ++launches) {  // positions in chunks, one launch each: no single launch holds the device for long
     const u64 p1 = std::min(qn, p0 + chunk);
-    if (timing) {
-      hipEvent_t e;
-      DG_HIP(hipEventCreate(&e));
-      lev.push_back(e);
-      DG_HIP(hipEventRecord(e, st));
-    }
+    DG_TRY(tm.launch(st));
     const dim3 grid(ceil_div(p1 - p0, TB));
     if (prm->mismatches == 0)
       hipLaunchKernelGGL(k_qmap<0>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, prm->forward_only, W, prm->max_count, p0, p1, (u32*)b.out, ctr);
@@ -566,14 +644,14 @@ static int query_map_impl(dg_index* ix, const dg_qmap_params* prm, const std::ve
     else
       hipLaunchKernelGGL(k_qmap<2>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, prm->forward_only, W, prm->max_count, p0, p1, (u32*)b.out, ctr);
   }
-  DG_HIP(hipEventRecord(ev[2], st));
+  DG_HIP(hipEventRecord(tm.ev[2], st));
   QmapCounters hc{};
   DG_HIP(hipMemcpyAsync(&hc, b.ctr, sizeof hc, hipMemcpyDeviceToHost, st));
   DG_HIP(hipMemcpyAsync(vals.data(), b.out, qn * 4, hipMemcpyDeviceToHost, st));
   DG_HIP(hipStreamSynchronize(st));
   DG_HIP(hipGetLastError());
-  float ms[2] = {0, 0};
-  for (int j = 0; j < 2; ++j) DG_HIP(hipEventElapsedTime(&ms[j], ev[j], ev[j + 1]));
+  float ms[2] = {0, 0}, longest = 0;
+  DG_TRY(tm.read(ms, &longest));
   stt->valid = hc.valid;
   stt->steps = hc.steps;
   stt->table_reads = hc.table_reads;
@@ -583,16 +661,72 @@ static int query_map_impl(dg_index* ix, const dg_qmap_params* prm, const std::ve
   stt->ms_valid = ms[0];
   stt->ms_search = ms[1];
   stt->ms_total = (double)ms[0] + (double)ms[1];  // in double: exactly the sum of the reported parts
-  if (!lev.empty()) {
-    float longest = 0;
-    for (size_t j = 0; j < lev.size(); ++j) {
-      float t = 0;
-      DG_HIP(hipEventElapsedTime(&t, lev[j], j + 1 < lev.size() ? lev[j + 1] : ev[2]));
-      longest = std::max(longest, t);
-    }
+  if (tm.timing && launches)
     std::fprintf(stderr, "dicey timing: query map e=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n", prm->mismatches,
                  (unsigned long long)launches, ms[1], longest);
+  return DG_OK;
+}
+
+// the same buffer with the A/C/G/T bitmap alone (a lane finds its own limit), k_qminlen per chunk of positions
+static int query_min_len_impl(dg_index* ix, const dg_qminlen_params* prm, const std::vector<u8>& hq, std::vector<u32>& vals,
+                              dg_qminlen_stats_t* stt) {
+  const FmView& f = ix->view;
+  const u64 qn = hq.size();
+  hipStream_t st = ix->stream;
+  QueryDev b(st);
+  DG_TRY(b.alloc("dg_query_min_len", qn, prm->max_k, 1, sizeof(QminlenCounters)));
+  u64 chunk = QMINLEN_CHUNK;
+  u32 W = MM_NARROW;
+  if (const char* e = exp_env("DICEY_QMINLEN_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
+  if (const char* e = exp_env("DICEY_MAP_NARROW")) W = (u32)std::min<u64>(std::strtoull(e, nullptr, 10), 0xFFFFFFFFull);
+  ChunkTimer tm;
+  DG_TRY(tm.init());
+  const u8* q = (const u8*)b.q;
+  const u64* acgt = b.acgt();
+  QminlenCounters* ctr = (QminlenCounters*)b.ctr;
+  const u32 TB = 256;
+  DG_HIP(hipMemsetAsync(b.ctr, 0, sizeof(QminlenCounters), st));
+  DG_HIP(hipEventRecord(tm.ev[0], st));
+  DG_TRY(b.upload(hq));
+  DG_HIP(hipEventRecord(tm.ev[1], st));
+  u64 launches = 0;
+  for (u64 p0 = 0; p0 < qn; p0 += chunk, ++launches) {  // positions in chunks, one launch each: no single launch holds the device for long
+    const u64 p1 = std::min(qn, p0 + chunk);
+    DG_TRY(tm.launch(st));
+    const dim3 grid(ceil_div(p1 - p0, TB));
+    if (prm->mismatches == 0)
+      hipLaunchKernelGGL(k_qminlen<0>, grid, dim3(TB), 0, st, f, q, acgt, b.nw, prm->min_k, prm->max_k, prm->forward_only, W, prm->at_most, p0, p1,
+                         (u32*)b.out, ctr);
+    else if (prm->mismatches == 1)
+      hipLaunchKernelGGL(k_qminlen<1>, grid, dim3(TB), 0, st, f, q, acgt, b.nw, prm->min_k, prm->max_k, prm->forward_only, W, prm->at_most, p0, p1,
+                         (u32*)b.out, ctr);
+    else
+      hipLaunchKernelGGL(k_qminlen<2>, grid, dim3(TB), 0, st, f, q, acgt, b.nw, prm->min_k, prm->max_k, prm->forward_only, W, prm->at_most, p0, p1,
+                         (u32*)b.out, ctr);
   }
+  DG_HIP(hipEventRecord(tm.ev[2], st));
+  QminlenCounters hc{};
+  DG_HIP(hipMemcpyAsync(&hc, b.ctr, sizeof hc, hipMemcpyDeviceToHost, st));
+  DG_HIP(hipMemcpyAsync(vals.data(), b.out, qn * 4, hipMemcpyDeviceToHost, st));
+  DG_HIP(hipStreamSynchronize(st));
+  DG_HIP(hipGetLastError());
+  float ms[2] = {0, 0}, longest = 0;
+  DG_TRY(tm.read(ms, &longest));
+  u64 found = 0;
+  for (u32 v : vals) found += v != 0 && v != QMAP_INVALID;
+  stt->valid = hc.valid;
+  stt->found = found;
+  stt->probes = hc.probes;
+  stt->steps = hc.steps;
+  stt->table_reads = hc.table_reads;
+  stt->verified_rows = hc.verified_rows;
+  stt->launches = launches;
+  stt->ms_valid = ms[0];
+  stt->ms_search = ms[1];
+  stt->ms_total = (double)ms[0] + (double)ms[1];  // in double: exactly the sum of the reported parts
+  if (tm.timing && launches)
+    std::fprintf(stderr, "dicey timing: query min length e=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n", prm->mismatches,
+                 (unsigned long long)launches, ms[1], longest);
   return DG_OK;
 }
 
@@ -660,32 +794,40 @@ int dg_query_map(dg_index* ix, const dg_qmap_params* p, const uint8_t* seqs, con
   if (p->flags || p->reserved[0] || p->reserved[1] || p->reserved[2]) return fail(DG_EINVAL, "dg_query_map: flags and reserved must be 0");
   if (p->k < 10 || p->k > 1000) return fail(DG_ELIMIT, "dg_query_map: k = %u outside 10..1000", p->k);
   if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_query_map: %u mismatches outside 0..2", p->mismatches);
+  DG_TRY(query_args_check("dg_query_map", ix, seqs, off, nseq, values, false));
   const u64 total = (off && nseq) ? off[nseq] : 0;
-  if (total >= (1ULL << 31) || (u64)nseq >= (1ULL << 31) || total + nseq >= (1ULL << 31))
-    return fail(DG_ELIMIT, "dg_query_map: %llu query bytes in %llu records: 2^31 or more with their separators", (unsigned long long)total,
-                (unsigned long long)nseq);
-  if (!ix || (nseq && !off) || (total && (!seqs || !values))) return fail(DG_EINVAL, "dg_query_map: null argument");
-  for (size_t i = 0; i < nseq; ++i)
-    if (off[i] > off[i + 1]) return fail(DG_EINVAL, "dg_query_map: offsets decrease at record %llu", (unsigned long long)i);
-  if (ix->view.n < 2 || ix->view.n > 0xFFFFFFFFull) return fail(DG_ELIMIT, "dg_query_map: index of %llu suffixes", (unsigned long long)ix->view.n);
-  if (any_lane_busy(ix)) return fail(DG_EINVAL, "dg_query_map: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)");
   dg_qmap_stats_t st{};
   st.positions = nseq ? total - off[0] : 0;
   if (total) {
     DG_HIP(hipSetDevice(ix->device));
-    const u64 base = off[0];
-    std::vector<u8> hq(total - base + nseq);  // record i at off[i] - base + i, a '\n' behind each
-    for (size_t i = 0; i < nseq; ++i) {
-      const u64 len = off[i + 1] - off[i];
-      if (len) std::memcpy(&hq[off[i] - base + i], seqs + off[i], len);
-      hq[off[i + 1] - base + i] = '\n';
-    }
+    const std::vector<u8> hq = query_pack(seqs, off, nseq);
     std::vector<u32> vals(hq.size());
     DG_TRY(query_map_impl(ix, p, hq, vals, &st));
-    for (size_t i = 0; i < nseq; ++i) {
-      const u64 len = off[i + 1] - off[i];
-      if (len) std::memcpy(values + off[i], &vals[off[i] - base + i], len * 4);
-    }
+    query_unpack(vals, off, nseq, values);
+  }
+  if (stats) *stats = st;
+  return DG_OK;
+}
+
+int dg_query_min_len(dg_index* ix, const dg_qminlen_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
+                     dg_qminlen_stats_t* stats) {
+  if (!p) return fail(DG_EINVAL, "dg_query_min_len: null argument");
+  if (p->flags || p->reserved[0] || p->reserved[1]) return fail(DG_EINVAL, "dg_query_min_len: flags and reserved must be 0");
+  if (p->min_k < 10 || p->min_k > 1000) return fail(DG_ELIMIT, "dg_query_min_len: min_k = %u outside 10..1000", p->min_k);
+  if (p->max_k < 10 || p->max_k > 1000) return fail(DG_ELIMIT, "dg_query_min_len: max_k = %u outside 10..1000", p->max_k);
+  if (p->min_k > p->max_k) return fail(DG_ELIMIT, "dg_query_min_len: min_k = %u above max_k = %u", p->min_k, p->max_k);
+  if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_query_min_len: %u mismatches outside 0..2", p->mismatches);
+  if (p->at_most > 0xFFFFFFFDu) return fail(DG_ELIMIT, "dg_query_min_len: at_most = %u above 4294967293", p->at_most);
+  DG_TRY(query_args_check("dg_query_min_len", ix, seqs, off, nseq, values, true));
+  const u64 total = (off && nseq) ? off[nseq] : 0;
+  dg_qminlen_stats_t st{};
+  st.positions = nseq ? total - off[0] : 0;
+  if (total) {
+    DG_HIP(hipSetDevice(ix->device));
+    const std::vector<u8> hq = query_pack(seqs, off, nseq);
+    std::vector<u32> vals(hq.size());
+    DG_TRY(query_min_len_impl(ix, p, hq, vals, &st));
+    query_unpack(vals, off, nseq, values);
   }
   if (stats) *stats = st;
   return DG_OK;

@@ -42,7 +42,8 @@ extern "C" {
  * 7 (additive exports, same version): dg_mappability, dg_map_values, dg_map_runs, dg_map_device_values, dg_map_stats, dg_map_free
  * 7 (additive exports, same version): dg_mappability_mm, dg_map_mm_stats ((k,e)-mappability, up to two mismatches)
  * 7 (additive exports, same version): dg_query_map (the same counts for the k-mers of sequences outside the index)
- * 7 (additive exports, same version): dg_min_unique (the shortest unique k-mer at each position) */
+ * 7 (additive exports, same version): dg_min_unique (the shortest unique k-mer at each position)
+ * 7 (additive exports, same version): dg_query_min_len (the shortest specific k-mer at each position of sequences outside the index) */
 #define DG_ABI_VERSION 7
 
 enum {
@@ -572,6 +573,48 @@ typedef struct {
 } dg_qmap_stats_t;
 int dg_query_map(dg_index* ix, const dg_qmap_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
                  dg_qmap_stats_t* stats /* may be NULL */);
+
+/* ABI 7, additive.  Query minimum length: how long must an oligo that starts at p of a record be before at most `at_most` places of the
+ * genome are within `mismatches` substitutions of it?  Records, bytes and the layout of `values` as for dg_query_map.  For a record Q and a
+ * position p:
+ *   run(p)     = the number of consecutive A/C/G/T bytes of Q from p (the record's end ends a run),   limit(p) = min(run(p), max_k),
+ *   value_k(p) = what dg_query_map returns at p for this k, mismatches and forward_only with max_count = 0,
+ *   len(p)     = DG_QMAP_INVALID when limit(p) < min_k (no k-mer of the smallest length starts there), otherwise
+ *                the smallest k in [min_k, limit(p)] with value_k(p) <= at_most, and 0 when there is none (still not specific at limit(p)).
+ * at_most = 0 asks for "absent from the genome" (off-target design), at_most = 1 for "at most one place" (for a cut of the genome: unique,
+ * with mismatches, which dg_min_unique does not offer).  value_k(p) never rises with k (a window within e of the (k+1)-mer has its
+ * k-prefix within e of the k-mer; on the other strand the window one further right), so the device searches per position instead of
+ * scanning every k: one call where a scan of dg_query_map needs max_k - min_k + 1.  Runs on the handle's stream, positions in chunks of
+ * launches; needs the query bytes, 4 bytes per position and one bitmap of free HBM (DG_ENOMEM before any kernel otherwise).  nseq = 0
+ * succeeds and writes nothing.  Checked in this order, the parameter block before the handle: a null parameter block, non-zero flags or
+ * reserved DG_EINVAL; min_k or max_k outside 10..1000, min_k > max_k, mismatches > 2 or at_most > 0xFFFFFFFD DG_ELIMIT; off[nseq] + nseq
+ * >= 2^31 DG_ELIMIT; no usable HIP device DG_ENODEV; a null handle, null seqs / off / values (where there is something to read or write)
+ * or decreasing offsets DG_EINVAL; then DG_EINVAL while a dg_hunt_submit batch is in flight on the handle.  On every failure `values` is
+ * left untouched. */
+typedef struct {
+  uint32_t min_k;       /* smallest length tried, 10..1000 */
+  uint32_t max_k;       /* largest length tried, min_k..1000 */
+  uint32_t mismatches;  /* e: 0, 1 or 2 substitutions */
+  int32_t forward_only; /* count the k-mer alone, not its reverse complement */
+  uint32_t at_most;     /* t: a length is specific when its value is <= t; 0..0xFFFFFFFD */
+  uint32_t flags;       /* 0 */
+  uint32_t reserved[2]; /* 0 */
+} dg_qminlen_params;
+typedef struct {
+  uint64_t positions;     /* off[nseq] - off[0]: values written */
+  uint64_t valid;         /* positions with limit(p) >= min_k (the others hold DG_QMAP_INVALID) */
+  uint64_t found;         /* positions with a length (neither 0 nor DG_QMAP_INVALID) */
+  uint64_t probes;        /* (position, k) pairs searched */
+  uint64_t steps;         /* backward-search steps (one pair of Occ lines each, all four characters) */
+  uint64_t table_reads;   /* K-mer table entries read */
+  uint64_t verified_rows; /* suffix-array rows finished on the text */
+  uint64_t launches;      /* launches of the search (positions go through in chunks) */
+  double ms_valid;        /* device time: upload of the queries and the A/C/G/T bitmap */
+  double ms_search;       /* device time of the search */
+  double ms_total;        /* ms_valid + ms_search */
+} dg_qminlen_stats_t;
+int dg_query_min_len(dg_index* ix, const dg_qminlen_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
+                     dg_qminlen_stats_t* stats /* may be NULL */);
 
 const char* dg_last_error(void);
 int dg_abi_version(void);

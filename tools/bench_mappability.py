@@ -10,7 +10,10 @@ k = K: a bisection over 10..1000 needs seven of those.  With --query the runs go
 outside the index): one query set of 1 Mb cut from the genome with 1 % substitutions plus 1 Mb random, in records of 10 kb, at e = 0, 1, 2
 per k, positions/s from the call's wall time and from the device time, the search counters per valid position, the longest launch — and,
 at e = 0 in the same run, the route a build without dg_query_map offers to the same numbers: dg_count on every k-mer and its reverse
-complement (cut out on the host, uploaded k-fold).  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
+complement (cut out on the host, uploaded k-fold).  With --query-minlen [--mismatches e] [--atmost t[,t..]] [--mink a --maxk b] [--no-scan] the same query
+set goes through dg_query_min_len (the shortest specific k-mer per position), one warm-up call in front of the timed one: device and wall
+ms, probes per valid position, the longest launch -- and beside it the route a build without it offers: one dg_query_map(k, max_count =
+t + 1) per k in [a, b], combined on the host; `same_values` compares the two.  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
 Prints one JSON line."""
 import argparse, ctypes as C, json, os, re, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,6 +32,10 @@ ap.add_argument("--min-unique", action="store_true", help="time dg_min_unique (m
 ap.add_argument("--maxk", type=int, default=100, help="max_k of --min-unique")
 ap.add_argument("--query", action="store_true", help="time dg_query_map on a 2 Mb query set (per k of --ks, e = 0, 1, 2) beside dg_count on its k-mers")
 ap.add_argument("--query-mb", type=float, default=1.0, help="Mb of each half of the --query set (cut from the genome / random)")
+ap.add_argument("--query-minlen", action="store_true", help="time dg_query_min_len (--mink..--maxk, --mismatches, --atmost) beside a per-k scan of dg_query_map")
+ap.add_argument("--mink", type=int, default=10, help="min_k of --query-minlen")
+ap.add_argument("--atmost", default="0", help="at_most of --query-minlen; a comma-separated list gives one run each")
+ap.add_argument("--no-scan", action="store_true", help="--query-minlen: skip the per-k scan of dg_query_map beside the call")
 ap.add_argument("--maxcount", type=int, default=0, help="max_count of the runs (0 = exact values)")
 ap.add_argument("--forward", choices=["both", "no", "yes"], default="both", help="which strand settings to time")
 ap.add_argument("--keep-index", action="store_true", help="leave the generated index (and its .lens.json) in --workdir for --fm9 runs")
@@ -171,7 +178,62 @@ def query_runs(k, recs):
     print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
 
 
-if a.query:
+def query_minlen_run(recs, t):
+    import numpy as np
+    buf = b"".join(recs)
+    off = np.zeros(len(recs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(r) for r in recs])
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    offp = off.ctypes.data_as(u64p)
+    INV = _capi.DG_QMAP_INVALID
+    e = a.mismatches
+    got = np.zeros(len(buf), dtype=np.uint32)
+    prm = _capi.QminlenParams(a.mink, a.maxk, e, 0, t, 0, (C.c_uint32 * 2)(0, 0))
+    st = _capi.QminlenStats()
+    _capi.check(L, L.dg_query_min_len(ix.handle, C.byref(prm), buf, offp, len(recs), got.ctypes.data_as(u32p), None))  # (warm-up)
+    os.environ["DICEY_TIMING"] = "1"
+    t0 = time.time()
+    err = stderr_of(lambda: _capi.check(L, L.dg_query_min_len(ix.handle, C.byref(prm), buf, offp, len(recs), got.ctypes.data_as(u32p), C.byref(st))))
+    wall = time.time() - t0
+    del os.environ["DICEY_TIMING"]
+    line = re.search(r"query min length e=\d+: (\d+) launches of the search, [0-9.]+ ms in all, longest ([0-9.]+) ms", err)
+    v = max(st.valid, 1)
+    run = {"query_minlen": True, "min_k": a.mink, "max_k": a.maxk, "mismatches": e, "at_most": t, "positions": st.positions, "valid": st.valid,
+           "found": st.found, "wall_ms": round(wall * 1e3, 2), "ms_total": round(st.ms_total, 2), "ms_valid": round(st.ms_valid, 2),
+           "ms_search": round(st.ms_search, 2), "launches": st.launches, "longest_launch_ms": float(line.group(2)) if line else None,
+           "probes_per_position": round(st.probes / v, 2), "steps_per_position": round(st.steps / v, 2),
+           "table_reads_per_position": round(st.table_reads / v, 2), "verified_rows_per_position": round(st.verified_rows / v, 2)}
+    if a.no_scan:
+        return run
+    # the route without dg_query_min_len: one dg_query_map per k with max_count = t + 1, the first k with a value <= t taken on the host
+    vals = np.zeros(len(buf), dtype=np.uint32)
+    qp = _capi.QmapParams(a.mink, e, 0, t + 1, 0, (C.c_uint32 * 3)(0, 0, 0))
+    _capi.check(L, L.dg_query_map(ix.handle, C.byref(qp), buf, offp, 1, vals.ctypes.data_as(u32p), None))  # (warm-up: one record)
+    scan = None
+    dev_ms = 0.0
+    t0 = time.time()
+    for k in range(a.mink, a.maxk + 1):
+        qp = _capi.QmapParams(k, e, 0, t + 1, 0, (C.c_uint32 * 3)(0, 0, 0))
+        qs = _capi.QmapStats()
+        _capi.check(L, L.dg_query_map(ix.handle, C.byref(qp), buf, offp, len(recs), vals.ctypes.data_as(u32p), C.byref(qs)))
+        dev_ms += qs.ms_total
+        if scan is None:
+            scan = np.where(vals == INV, INV, 0).astype(np.uint32)
+        scan[(scan == 0) & (vals != INV) & (vals <= t)] = k
+    scan_wall = time.time() - t0
+    run.update({"scan_calls": a.maxk - a.mink + 1, "scan_wall_ms": round(scan_wall * 1e3, 2), "scan_ms_total": round(dev_ms, 2),
+                "same_values": bool((scan == got).all()), "scan_over_call_wall": round(scan_wall / max(wall, 1e-9), 2),
+                "scan_over_call_device": round(dev_ms / max(st.ms_total, 1e-9), 2)})
+    return run
+
+
+if a.query_minlen:
+    recs = query_set()
+    for t in [int(x) for x in a.atmost.split(",")]:
+        runs.append(query_minlen_run(recs, t))
+        print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+    ks = []
+elif a.query:
     recs = query_set()
     for k in [int(x) for x in a.ks.split(",")]:
         query_runs(k, recs)
@@ -219,7 +281,7 @@ ix.close()
 # the CLI end to end: open + map + runs + format + gzip
 stem = os.path.join(a.workdir, "dicey_map_bench_cli_%s" % a.genome)
 gz = stem + ".bedgraph.gz"
-if a.cli_k and not a.min_unique and not a.query:
+if a.cli_k and not a.min_unique and not a.query and not a.query_minlen:
     with open(stem + ".fa", "w") as f:
         f.write(">chr1\nN\n")
     with open(stem + ".fa.fai", "w") as f:
