@@ -227,19 +227,26 @@ class FmIndex:
             self._L.dg_map_free(m)
 
     def query_mappability(self, seqs: Sequence, k: int = 100, forward_only: bool = False, max_count: int = 0, mismatches: int = 0,
-                          stats: Optional[dict] = None):
+                          stats: Optional[dict] = None, anchor: Optional[int] = None):
         """k-mer counts for sequences that are NOT in the index (include/dicey_gpu.h dg_query_map): a list with one numpy uint32 array
         per record, value[p] = the number of windows of the genome within Hamming distance `mismatches` (0..2) of the k-mer w at p of the
         record, plus those within it of revcomp(w) (w alone with forward_only); 0 = absent from the genome; QMAP_INVALID where p + k runs
         past the record or w holds a byte other than A/C/G/T; min(value, max_count) when max_count > 0.  str records are upper-cased,
-        bytes go through as given.  `stats`, when given, receives dg_qmap_stats_t."""
+        bytes go through as given.  `stats`, when given, receives dg_qmap_stats_t.  With `anchor` = a (0..k; dg_query_map_anchored) only
+        windows that match the LAST a bases of w, the oligo's 3' end, exactly are counted; on the other strand these are the first a
+        bases of the window.  None calls dg_query_map."""
         import numpy as np
         recs = [s.upper().encode() if isinstance(s, str) else bytes(s) for s in seqs]
         buf, off = _pack(recs)
         out = np.zeros(len(buf), dtype=np.uint32)
-        prm = _capi.QmapParams(k, mismatches, 1 if forward_only else 0, max_count, 0, (C.c_uint32 * 3)(0, 0, 0))
         st = _capi.QmapStats()
-        _capi.check(self._L, self._L.dg_query_map(self._h, C.byref(prm), buf, off, len(recs), out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st)))
+        outp = out.ctypes.data_as(C.POINTER(C.c_uint32))
+        if anchor is None:
+            prm = _capi.QmapParams(k, mismatches, 1 if forward_only else 0, max_count, 0, (C.c_uint32 * 3)(0, 0, 0))
+            _capi.check(self._L, self._L.dg_query_map(self._h, C.byref(prm), buf, off, len(recs), outp, C.byref(st)))
+        else:
+            prm = _capi.QmapAnchorParams(k, mismatches, anchor, 1 if forward_only else 0, max_count, 0, (C.c_uint32 * 2)(0, 0))
+            _capi.check(self._L, self._L.dg_query_map_anchored(self._h, C.byref(prm), buf, off, len(recs), outp, C.byref(st)))
         if stats is not None:
             stats.update({f: getattr(st, f) for f, _ in _capi.QmapStats._fields_})
         return [out[off[i]:off[i + 1]].copy() for i in range(len(recs))]

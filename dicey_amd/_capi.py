@@ -113,6 +113,11 @@ class QmapStats(C.Structure):
                 ("ms_search", C.c_double), ("ms_total", C.c_double)]
 
 
+class QmapAnchorParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("mismatches", C.c_uint32), ("anchor", C.c_uint32), ("forward_only", C.c_int32),
+                ("max_count", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class QminlenParams(C.Structure):
     _fields_ = [("min_k", C.c_uint32), ("max_k", C.c_uint32), ("mismatches", C.c_uint32), ("forward_only", C.c_int32),
                 ("at_most", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
@@ -149,7 +154,8 @@ SYMBOLS = ["dg_index_open", "dg_index_close", "dg_index_stats", "dg_count", "dg_
            "dg_neighbors", "dg_buffer_free", "dg_hit_rows", "dg_hunt_rows", "dg_hunt_submit", "dg_hunt_wait", "dg_hunt_device_submit",
            "dg_chit_unpack", "dg_normalize_query", "dg_hunt_expand", "dg_index_stream", "dg_fm9_check",
            "dg_mappability", "dg_map_values", "dg_map_runs", "dg_map_device_values", "dg_map_stats", "dg_map_free",
-           "dg_mappability_mm", "dg_map_mm_stats", "dg_min_unique", "dg_query_map", "dg_query_min_len"]
+           "dg_mappability_mm", "dg_map_mm_stats", "dg_min_unique", "dg_query_map", "dg_query_min_len",
+           "dg_query_map_anchored"]
 
 _lib = None
 
@@ -228,6 +234,7 @@ def load(path=None):
     L.dg_min_unique.argtypes = [vp, C.POINTER(MinUniqueParams), C.POINTER(vp)]
     L.dg_query_map.argtypes = [vp, C.POINTER(QmapParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapStats)]
     L.dg_query_min_len.argtypes = [vp, C.POINTER(QminlenParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QminlenStats)]
+    L.dg_query_map_anchored.argtypes = [vp, C.POINTER(QmapAnchorParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapStats)]
     L.dg_map_free.restype = None
     if path is None:
         _lib = L

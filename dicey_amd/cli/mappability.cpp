@@ -5,6 +5,7 @@
 // With -u the value is the minimum unique length instead (dg_min_unique): the shortest k-mer that starts at the position and is unique.
 // With -q the positions are those of the records of a second FASTA file, which need not be in the genome (dg_query_map): zero is a value there.
 // With -q -l the value is the query minimum length (dg_query_min_len): the shortest k-mer from the position with at most -t places in the genome.
+// With -q -a the last -a bases of every k-mer, the oligo's 3' end, must match exactly (dg_query_map_anchored).
 #include <zlib.h>
 
 #include <algorithm>
@@ -24,7 +25,7 @@ const OptSpec kMapOpts[] = {{"help", '?', false},  {"genome", 'g', true},  {"kme
                             {"forward", 'f', false}, {"maxcount", 'c', true}, {"outfile", 'o', true},
                             {"mismatches", 'e', true}, {"minunique", 'u', false},
                             {"query", 'q', true}, {"minlength", 'l', false}, {"shortest", 's', true},
-                            {"atmost", 't', true}};
+                            {"atmost", 't', true}, {"anchor", 'a', true}};
 
 void map_usage() {
   std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz [-q targets.fa.gz]" << std::endl;
@@ -40,6 +41,7 @@ void map_usage() {
                "  -l [ --minlength ]                 with -q: write the shortest specific length instead; -k is then the largest length tried\n"
                "  -s [ --shortest ] arg (=10)        with -l: the smallest length tried (10..1000, at most -k)\n"
                "  -t [ --atmost ] arg (=0)           with -l: a length is specific when its k-mer has at most this many places in the genome\n"
+               "  -a [ --anchor ] arg                with -q: the last arg bases of every k-mer must match exactly (0..-k)\n"
                "  -o [ --outfile ] arg               gzipped output file (default: plain text on stdout)\n"
                "\n"
                "Output: bedGraph lines name, start, end, value (0-based, end exclusive) of maximal runs of equal values, where the value\n"
@@ -59,6 +61,10 @@ void map_usage() {
                "there) at which the genome holds at most -t k-mers within -e mismatches of the record's k-mer and of its reverse complement\n"
                "(-f: of the k-mer alone): -t 0 asks how long an oligo must be to have no place in the genome, -t 1 for at most one place.\n"
                "Positions without such a length, and positions where not even a k-mer of length -s starts, have no line.\n"
+               "With -q -a only the k-mers of the genome that match the LAST -a bases of the record's k-mer, the 3' end of the oligo, exactly\n"
+               "are counted: the places a primer could extend from or a guide's seed could bind.  On the other strand the genome shows these\n"
+               "bases, reverse-complemented, as the first -a of its k-mer.  -a 0 writes what -q alone writes, -a equal to -k what -e 0 writes.\n"
+               "-a cannot be combined with -l: with an anchored 3' end a longer oligo can have more places than a shorter one.\n"
                "\n";
 }
 
@@ -117,8 +123,9 @@ bool read_fasta(const std::string& path, std::vector<std::string>& names, std::v
 }
 
 // bedGraph of the query records: one line per maximal run of equal values over valid positions, zero included.  With lp (-l) the values
-// are minimum lengths and zero, no length, has no line either
-int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_params* lp, const std::string& query, const std::string& outfile) {
+// are minimum lengths and zero, no length, has no line either; with ap (-a) they are the anchored counts
+int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_params* lp, const dg_qmap_anchor_params* ap, const std::string& query,
+                    const std::string& outfile) {
   std::vector<std::string> names, seqs;
   if (!read_fasta(query, names, seqs)) return bail("Error: Could not read any sequence from " + query + "!");
   std::vector<uint64_t> off(seqs.size() + 1, 0);
@@ -127,8 +134,9 @@ int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_par
   all.reserve(off.back());
   for (const std::string& s : seqs) all += s;
   std::vector<uint32_t> val(off.back());
-  const int rc = lp ? dg_query_min_len(ix, lp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
-                    : dg_query_map(ix, &qp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr);
+  const int rc = lp   ? dg_query_min_len(ix, lp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
+                 : ap ? dg_query_map_anchored(ix, ap, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
+                      : dg_query_map(ix, &qp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr);
   if (rc != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
   FILE* fo = stdout;
   if (!outfile.empty()) {
@@ -207,8 +215,8 @@ int mappability_main(int argc, char** argv) {
   }
   std::string genome, outfile, query;
   bool help = false, have_genome = false, forward = false, minunique = false, have_query = false, minlength = false, have_shortest = false,
-       have_atmost = false;
-  long long k = 100, maxcount = 0, mismatches = 0, shortest = 10, atmost = 0;
+       have_atmost = false, have_anchor = false;
+  long long k = 100, maxcount = 0, mismatches = 0, shortest = 10, atmost = 0, anchor = 0;
   for (auto& kv : p.kv) {
     if (kv.first == "help") help = true;
     else if (kv.first == "genome") { genome = kv.second; have_genome = true; }
@@ -222,6 +230,7 @@ int mappability_main(int argc, char** argv) {
     else if (kv.first == "minlength") minlength = true;
     else if (kv.first == "shortest") { shortest = std::strtoll(kv.second.c_str(), nullptr, 10); have_shortest = true; }
     else if (kv.first == "atmost") { atmost = std::strtoll(kv.second.c_str(), nullptr, 10); have_atmost = true; }
+    else if (kv.first == "anchor") { anchor = std::strtoll(kv.second.c_str(), nullptr, 10); have_anchor = true; }
   }
   if (help || !have_genome || !p.positional.empty()) {
     map_usage();
@@ -238,6 +247,9 @@ int mappability_main(int argc, char** argv) {
   if (shortest < 10 || shortest > 1000) return bail("Error: shortest length " + std::to_string(shortest) + " outside 10..1000!");
   if (shortest > k) return bail("Error: shortest length " + std::to_string(shortest) + " above the largest length " + std::to_string(k) + " (-k)!");
   if (atmost < 0 || atmost > 0xFFFFFFFDll) return bail("Error: atmost " + std::to_string(atmost) + " outside 0..4294967293!");
+  if (have_anchor && !have_query) return bail("Error: --anchor needs --query!");
+  if (have_anchor && minlength) return bail("Error: --anchor cannot be combined with --minlength!");
+  if (have_anchor && (anchor < 0 || anchor > k)) return bail("Error: anchor " + std::to_string(anchor) + " outside 0.." + std::to_string(k) + " (-k)!");
   if (!file_nonempty(genome)) return bail("Error: Genome does not exist!");
   if (have_query && !file_nonempty(query)) return bail("Error: Query file " + query + " does not exist or is empty!");
   std::vector<uint32_t> seqlen;
@@ -263,7 +275,8 @@ int mappability_main(int argc, char** argv) {
   if (have_query) {
     const dg_qmap_params qp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, {0u, 0u, 0u}};
     const dg_qminlen_params lp = {(uint32_t)shortest, (uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)atmost, 0u, {0u, 0u}};
-    return write_query_map(ix, qp, minlength ? &lp : nullptr, query, outfile);
+    const dg_qmap_anchor_params ap = {(uint32_t)k, (uint32_t)mismatches, (uint32_t)anchor, forward ? 1 : 0, (uint32_t)maxcount, 0u, {0u, 0u}};
+    return write_query_map(ix, qp, minlength ? &lp : nullptr, have_anchor ? &ap : nullptr, query, outfile);
   }
   dg_map_mm_params mp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, 0u};
   dg_min_unique_params up = {(uint32_t)k, forward ? 1 : 0, 0u, 0u};

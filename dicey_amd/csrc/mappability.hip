@@ -17,7 +17,8 @@
 // is 1, from one pass over neighbouring suffixes and one backward search per rank.
 // dg_query_map (query_map.hpp) runs phase 1 on a buffer of query records laid out like the text and then one search per valid position
 // of it: the (k,e) counts of k-mers that are not in the index.  dg_query_min_len (query_min_len.hpp) looks, on the same buffer, for the
-// smallest k at which that count is at most t.
+// smallest k at which that count is at most t.  dg_query_map_anchored (query_anchor.hpp) is dg_query_map with the last a bases of every
+// k-mer matched exactly.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -208,6 +209,7 @@ __global__ void __launch_bounds__(256) k_heads(FmView f, u32 k, int forward_only
 #include "map_mm.hpp"  // k_heads' sibling for e >= 1 mismatches
 #include "query_map.hpp"  // the same search per position of a query buffer (dg_query_map)
 #include "query_min_len.hpp"  // and the search for the smallest specific k per position (dg_query_min_len)
+#include "query_anchor.hpp"  // k_qmap with the k-mer's last bases matched exactly (dg_query_map_anchored)
 namespace dg {
 
 // out[SA[i]] = the total of i's group (heads hold it in their own slot; members hold their head's rank), 0 for invalid ranks
@@ -606,14 +608,16 @@ struct ChunkTimer {
   }
 };
 
-// hq: the records as REC1 '\n' REC2 '\n' ... (qn bytes); vals: u32[qn], one value per buffer position
-static int query_map_impl(dg_index* ix, const dg_qmap_params* prm, const std::vector<u8>& hq, std::vector<u32>& vals, dg_qmap_stats_t* stt) {
+// hq: the records as REC1 '\n' REC2 '\n' ... (qn bytes); vals: u32[qn], one value per buffer position.  anchor: null for dg_query_map
+// (k_qmap), else the number of last bases matched exactly (k_qmap_anch): the same buffers, chunks and W either way
+static int query_map_impl(const char* who, dg_index* ix, const dg_qmap_params* prm, const u32* anchor, const std::vector<u8>& hq, std::vector<u32>& vals,
+                          dg_qmap_stats_t* stt) {
   const FmView& f = ix->view;
   const u64 qn = hq.size();
   const u32 k = prm->k;
   hipStream_t st = ix->stream;
   QueryDev b(st);
-  DG_TRY(b.alloc("dg_query_map", qn, k, 2, sizeof(QmapCounters)));
+  DG_TRY(b.alloc(who, qn, k, 2, sizeof(QmapCounters)));
   u64 chunk = QMAP_CHUNK;
   u32 W = MM_NARROW;
   if (const char* e = exp_env("DICEY_QMAP_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
@@ -637,7 +641,17 @@ static int query_map_impl(dg_index* ix, const dg_qmap_params* prm, const std::ve
     const u64 p1 = std::min(qn, p0 + chunk);
     DG_TRY(tm.launch(st));
     const dim3 grid(ceil_div(p1 - p0, TB));
-    if (prm->mismatches == 0)
+    if (anchor) {
+      if (prm->mismatches == 0)
+        hipLaunchKernelGGL(k_qmap_anch<0>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, *anchor, prm->forward_only, W, prm->max_count, p0, p1,
+                           (u32*)b.out, ctr);
+      else if (prm->mismatches == 1)
+        hipLaunchKernelGGL(k_qmap_anch<1>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, *anchor, prm->forward_only, W, prm->max_count, p0, p1,
+                           (u32*)b.out, ctr);
+      else
+        hipLaunchKernelGGL(k_qmap_anch<2>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, *anchor, prm->forward_only, W, prm->max_count, p0, p1,
+                           (u32*)b.out, ctr);
+    } else if (prm->mismatches == 0)
       hipLaunchKernelGGL(k_qmap<0>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, prm->forward_only, W, prm->max_count, p0, p1, (u32*)b.out, ctr);
     else if (prm->mismatches == 1)
       hipLaunchKernelGGL(k_qmap<1>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, prm->forward_only, W, prm->max_count, p0, p1, (u32*)b.out, ctr);
@@ -661,7 +675,10 @@ static int query_map_impl(dg_index* ix, const dg_qmap_params* prm, const std::ve
   stt->ms_valid = ms[0];
   stt->ms_search = ms[1];
   stt->ms_total = (double)ms[0] + (double)ms[1];  // in double: exactly the sum of the reported parts
-  if (tm.timing && launches)
+  if (tm.timing && launches && anchor)
+    std::fprintf(stderr, "dicey timing: query map e=%u anchor=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n", prm->mismatches,
+                 *anchor, (unsigned long long)launches, ms[1], longest);
+  else if (tm.timing && launches)
     std::fprintf(stderr, "dicey timing: query map e=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n", prm->mismatches,
                  (unsigned long long)launches, ms[1], longest);
   return DG_OK;
@@ -802,7 +819,30 @@ int dg_query_map(dg_index* ix, const dg_qmap_params* p, const uint8_t* seqs, con
     DG_HIP(hipSetDevice(ix->device));
     const std::vector<u8> hq = query_pack(seqs, off, nseq);
     std::vector<u32> vals(hq.size());
-    DG_TRY(query_map_impl(ix, p, hq, vals, &st));
+    DG_TRY(query_map_impl("dg_query_map", ix, p, nullptr, hq, vals, &st));
+    query_unpack(vals, off, nseq, values);
+  }
+  if (stats) *stats = st;
+  return DG_OK;
+}
+
+int dg_query_map_anchored(dg_index* ix, const dg_qmap_anchor_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
+                          dg_qmap_stats_t* stats) {
+  if (!p) return fail(DG_EINVAL, "dg_query_map_anchored: null argument");
+  if (p->flags || p->reserved[0] || p->reserved[1]) return fail(DG_EINVAL, "dg_query_map_anchored: flags and reserved must be 0");
+  if (p->k < 10 || p->k > 1000) return fail(DG_ELIMIT, "dg_query_map_anchored: k = %u outside 10..1000", p->k);
+  if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_query_map_anchored: %u mismatches outside 0..2", p->mismatches);
+  if (p->anchor > p->k) return fail(DG_ELIMIT, "dg_query_map_anchored: anchor = %u above k = %u", p->anchor, p->k);
+  DG_TRY(query_args_check("dg_query_map_anchored", ix, seqs, off, nseq, values, true));
+  const u64 total = (off && nseq) ? off[nseq] : 0;
+  dg_qmap_stats_t st{};
+  st.positions = nseq ? total - off[0] : 0;
+  if (total) {
+    DG_HIP(hipSetDevice(ix->device));
+    const dg_qmap_params q = {p->k, p->mismatches, p->forward_only, p->max_count, 0u, {0u, 0u, 0u}};
+    const std::vector<u8> hq = query_pack(seqs, off, nseq);
+    std::vector<u32> vals(hq.size());
+    DG_TRY(query_map_impl("dg_query_map_anchored", ix, &q, &p->anchor, hq, vals, &st));
     query_unpack(vals, off, nseq, values);
   }
   if (stats) *stats = st;

@@ -616,6 +616,32 @@ typedef struct {
 int dg_query_min_len(dg_index* ix, const dg_qminlen_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
                      dg_qminlen_stats_t* stats /* may be NULL */);
 
+/* ABI 7, additive.  Anchored query mappability: dg_query_map with the LAST `anchor` bases of every k-mer, the oligo's 3' end, matched
+ * exactly: the places within e mismatches that a primer could extend from or a guide's seed could bind.  Records, bytes, validity,
+ * DG_QMAP_INVALID, saturation, max_count, forward_only, the layout of `values` and the statistics are dg_query_map's.  For w = Q[p, p+k):
+ *   fwd(p) = #{valid windows u of the text : Hamming(u, w) <= e and u[k-a, k) == w[k-a, k)}
+ *   rev(p) = #{valid windows u of the text : Hamming(u, revcomp(w)) <= e and u[0, a) == revcomp(w)[0, a)}
+ *   value(p) = fwd(p) + rev(p)   (forward_only: fwd(p)).
+ * The anchored bases are always the last a of the oligo w; on the other strand the text shows them as the FIRST a bases of the window.
+ * anchor = 0 gives dg_query_map's values, anchor = k its e = 0 values, and the value never rises with the anchor.  It is NOT monotone
+ * in k for an oligo that grows at its 3' end (a site whose only mismatch is at offset k-1 is rejected at length k and accepted at
+ * k+1), so dg_query_min_len has no anchor.
+ * Checks, in this order: a null block, non-zero flags or reserved DG_EINVAL; k outside 10..1000, mismatches > 2 or anchor > k DG_ELIMIT;
+ * off[nseq] + nseq >= 2^31 DG_ELIMIT; no device DG_ENODEV; a null handle, null seqs / off / values (where there is something to read or
+ * write) or decreasing offsets DG_EINVAL; then DG_EINVAL while a dg_hunt_submit batch is in flight on the handle.  On every failure
+ * `values` is left untouched. */
+typedef struct {
+  uint32_t k;           /* k-mer length, 10..1000 */
+  uint32_t mismatches;  /* e: 0, 1 or 2 substitutions */
+  uint32_t anchor;      /* a: the last a bases of the k-mer match exactly, 0..k */
+  int32_t forward_only; /* non-zero: fwd(p) alone */
+  uint32_t max_count;   /* 0 = exact values, else min(value, max_count) */
+  uint32_t flags;       /* 0 */
+  uint32_t reserved[2]; /* 0 */
+} dg_qmap_anchor_params;
+int dg_query_map_anchored(dg_index* ix, const dg_qmap_anchor_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
+                          dg_qmap_stats_t* stats /* may be NULL */);
+
 const char* dg_last_error(void);
 int dg_abi_version(void);
 int dg_device_count(void);

@@ -10,7 +10,9 @@ k = K: a bisection over 10..1000 needs seven of those.  With --query the runs go
 outside the index): one query set of 1 Mb cut from the genome with 1 % substitutions plus 1 Mb random, in records of 10 kb, at e = 0, 1, 2
 per k, positions/s from the call's wall time and from the device time, the search counters per valid position, the longest launch — and,
 at e = 0 in the same run, the route a build without dg_query_map offers to the same numbers: dg_count on every k-mer and its reverse
-complement (cut out on the host, uploaded k-fold).  With --query-minlen [--mismatches e] [--atmost t[,t..]] [--mink a --maxk b] [--no-scan] the same query
+complement (cut out on the host, uploaded k-fold).  With --query --anchor A[,A..] the same query set goes through
+dg_query_map_anchored (the last A bases of every k-mer matched exactly; `k` stands for the k-mer length) beside dg_query_map at the same k and e.
+With --query-minlen [--mismatches e] [--atmost t[,t..]] [--mink a --maxk b] [--no-scan] the same query
 set goes through dg_query_min_len (the shortest specific k-mer per position), one warm-up call in front of the timed one: device and wall
 ms, probes per valid position, the longest launch -- and beside it the route a build without it offers: one dg_query_map(k, max_count =
 t + 1) per k in [a, b], combined on the host; `same_values` compares the two.  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
@@ -32,6 +34,8 @@ ap.add_argument("--min-unique", action="store_true", help="time dg_min_unique (m
 ap.add_argument("--maxk", type=int, default=100, help="max_k of --min-unique")
 ap.add_argument("--query", action="store_true", help="time dg_query_map on a 2 Mb query set (per k of --ks, e = 0, 1, 2) beside dg_count on its k-mers")
 ap.add_argument("--query-mb", type=float, default=1.0, help="Mb of each half of the --query set (cut from the genome / random)")
+ap.add_argument("--anchor", default="", help="with --query: time dg_query_map_anchored at these anchors (comma-separated; k = the k-mer length) beside "
+                "dg_query_map at the same k and e (e = 1, 2, or --mismatches when given)")
 ap.add_argument("--query-minlen", action="store_true", help="time dg_query_min_len (--mink..--maxk, --mismatches, --atmost) beside a per-k scan of dg_query_map")
 ap.add_argument("--mink", type=int, default=10, help="min_k of --query-minlen")
 ap.add_argument("--atmost", default="0", help="at_most of --query-minlen; a comma-separated list gives one run each")
@@ -178,6 +182,50 @@ def query_runs(k, recs):
     print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
 
 
+def query_anchor_runs(k, recs):
+    """dg_query_map, then dg_query_map_anchored per anchor of --anchor, on the same records: one warm-up call in front of every timed one"""
+    import numpy as np
+    buf = b"".join(recs)
+    off = np.zeros(len(recs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(r) for r in recs])
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    offp = off.ctypes.data_as(u64p)
+    anchors = [k if x == "k" else int(x) for x in a.anchor.split(",")]
+
+    def timed(call, prm):
+        vals = np.zeros(len(buf), dtype=np.uint32)
+        st = _capi.QmapStats()
+        _capi.check(L, call(ix.handle, C.byref(prm), buf, offp, len(recs), vals.ctypes.data_as(u32p), None))  # (warm-up)
+        t0 = time.time()
+        _capi.check(L, call(ix.handle, C.byref(prm), buf, offp, len(recs), vals.ctypes.data_as(u32p), C.byref(st)))
+        return vals, st, time.time() - t0
+
+    def row(st, wall):
+        v = max(st.valid, 1)
+        return {"valid": st.valid, "wall_ms": round(wall * 1e3, 2), "ms_total": round(st.ms_total, 2), "ms_search": round(st.ms_search, 2),
+                "launches": st.launches, "steps_per_position": round(st.steps / v, 2), "table_reads_per_position": round(st.table_reads / v, 2),
+                "verified_rows_per_position": round(st.verified_rows / v, 2)}
+
+    for e in ([a.mismatches] if a.mismatches else [1, 2]):
+        plain, st0, wall = timed(L.dg_query_map, _capi.QmapParams(k, e, 0, a.maxcount, 0, (C.c_uint32 * 3)(0, 0, 0)))
+        exact = timed(L.dg_query_map, _capi.QmapParams(k, 0, 0, a.maxcount, 0, (C.c_uint32 * 3)(0, 0, 0)))[0]
+        runs.append(dict({"query": True, "call": "dg_query_map", "k": k, "mismatches": e, "max_count": a.maxcount}, **row(st0, wall)))
+        print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+        prev = plain
+        for anc in anchors:
+            vals, st, wall = timed(L.dg_query_map_anchored, _capi.QmapAnchorParams(k, e, anc, 0, a.maxcount, 0, (C.c_uint32 * 2)(0, 0)))
+            ok = vals != _capi.DG_QMAP_INVALID
+            runs.append(dict({"query": True, "call": "dg_query_map_anchored", "k": k, "mismatches": e, "anchor": anc, "max_count": a.maxcount,
+                              "over_dg_query_map": round(st.ms_search / max(st0.ms_search, 1e-9), 3), "below_unanchored": int((vals[ok] < plain[ok]).sum()),
+                              "above_exact": int((vals[ok] > exact[ok]).sum()), "never_above_smaller_anchor": bool((vals <= prev).all())}, **row(st, wall)))
+            if anc == 0:
+                runs[-1]["same_values"] = bool((vals == plain).all())
+            if anc == k:
+                runs[-1]["same_values"] = bool((vals == exact).all())
+            prev = vals
+            print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+
+
 def query_minlen_run(recs, t):
     import numpy as np
     buf = b"".join(recs)
@@ -236,7 +284,10 @@ if a.query_minlen:
 elif a.query:
     recs = query_set()
     for k in [int(x) for x in a.ks.split(",")]:
-        query_runs(k, recs)
+        if a.anchor:
+            query_anchor_runs(k, recs)
+        else:
+            query_runs(k, recs)
     ks = []
 elif a.min_unique:
     for fo in STRANDS:
