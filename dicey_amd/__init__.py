@@ -270,6 +270,26 @@ class FmIndex:
             stats.update({f: getattr(st, f) for f, _ in _capi.QminlenStats._fields_})
         return [out[off[i]:off[i + 1]].copy() for i in range(len(recs))]
 
+    def query_min_length_end(self, seqs: Sequence, max_k: int = 100, min_k: int = 10, at_most: int = 0, mismatches: int = 0,
+                             anchor: int = 0, forward_only: bool = False, stats: Optional[dict] = None):
+        """The shortest specific oligo by its LAST base, per position of sequences that are NOT in the index (include/dicey_gpu.h
+        dg_query_min_len_end): a list with one numpy uint32 array per record, value[p] = the smallest k in min_k..min(max_k, the run of
+        A/C/G/T that ends at p) at which the k-mer that ENDS at p, a primer whose 3' end is p, has at most `at_most` places in the genome
+        within `mismatches` substitutions and with its last `anchor` bases (0..min_k) exact, i.e. at which
+        query_mappability(k, anchor=anchor)[p - k + 1] <= at_most; 0 = no such length; QMAP_INVALID where not even a min_k-mer of
+        A/C/G/T ends.  str records are upper-cased, bytes go through as given.  `stats`, when given, receives dg_qminlen_stats_t."""
+        import numpy as np
+        recs = [s.upper().encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        buf, off = _pack(recs)
+        out = np.zeros(len(buf), dtype=np.uint32)
+        prm = _capi.QminlenEndParams(min_k, max_k, mismatches, anchor, 1 if forward_only else 0, at_most, 0, (C.c_uint32 * 2)(0, 0))
+        st = _capi.QminlenStats()
+        _capi.check(self._L, self._L.dg_query_min_len_end(self._h, C.byref(prm), buf, off, len(recs),
+                                                          out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in _capi.QminlenStats._fields_})
+        return [out[off[i]:off[i + 1]].copy() for i in range(len(recs))]
+
     def _map_runs(self, m, lo, hi):
         import numpy as np
         nr = C.c_uint64()

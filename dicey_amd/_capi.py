@@ -123,6 +123,11 @@ class QminlenParams(C.Structure):
                 ("at_most", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class QminlenEndParams(C.Structure):
+    _fields_ = [("min_k", C.c_uint32), ("max_k", C.c_uint32), ("mismatches", C.c_uint32), ("anchor", C.c_uint32),
+                ("forward_only", C.c_int32), ("at_most", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class QminlenStats(C.Structure):
     _fields_ = [("positions", C.c_uint64), ("valid", C.c_uint64), ("found", C.c_uint64), ("probes", C.c_uint64), ("steps", C.c_uint64),
                 ("table_reads", C.c_uint64), ("verified_rows", C.c_uint64), ("launches", C.c_uint64), ("ms_valid", C.c_double),
@@ -155,7 +160,7 @@ SYMBOLS = ["dg_index_open", "dg_index_close", "dg_index_stats", "dg_count", "dg_
            "dg_chit_unpack", "dg_normalize_query", "dg_hunt_expand", "dg_index_stream", "dg_fm9_check",
            "dg_mappability", "dg_map_values", "dg_map_runs", "dg_map_device_values", "dg_map_stats", "dg_map_free",
            "dg_mappability_mm", "dg_map_mm_stats", "dg_min_unique", "dg_query_map", "dg_query_min_len",
-           "dg_query_map_anchored"]
+           "dg_query_map_anchored", "dg_query_min_len_end"]
 
 _lib = None
 
@@ -235,6 +240,7 @@ def load(path=None):
     L.dg_query_map.argtypes = [vp, C.POINTER(QmapParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapStats)]
     L.dg_query_min_len.argtypes = [vp, C.POINTER(QminlenParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QminlenStats)]
     L.dg_query_map_anchored.argtypes = [vp, C.POINTER(QmapAnchorParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapStats)]
+    L.dg_query_min_len_end.argtypes = [vp, C.POINTER(QminlenEndParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QminlenStats)]
     L.dg_map_free.restype = None
     if path is None:
         _lib = L

@@ -6,6 +6,7 @@
 // With -q the positions are those of the records of a second FASTA file, which need not be in the genome (dg_query_map): zero is a value there.
 // With -q -l the value is the query minimum length (dg_query_min_len): the shortest k-mer from the position with at most -t places in the genome.
 // With -q -a the last -a bases of every k-mer, the oligo's 3' end, must match exactly (dg_query_map_anchored).
+// With -q -l -E the length is that of the shortest specific k-mer that ENDS at the position, its last -a bases exact (dg_query_min_len_end).
 #include <zlib.h>
 
 #include <algorithm>
@@ -25,7 +26,8 @@ const OptSpec kMapOpts[] = {{"help", '?', false},  {"genome", 'g', true},  {"kme
                             {"forward", 'f', false}, {"maxcount", 'c', true}, {"outfile", 'o', true},
                             {"mismatches", 'e', true}, {"minunique", 'u', false},
                             {"query", 'q', true}, {"minlength", 'l', false}, {"shortest", 's', true},
-                            {"atmost", 't', true}, {"anchor", 'a', true}};
+                            {"atmost", 't', true}, {"anchor", 'a', true},
+                            {"byend", 'E', false}};
 
 void map_usage() {
   std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz [-q targets.fa.gz]" << std::endl;
@@ -42,6 +44,7 @@ void map_usage() {
                "  -s [ --shortest ] arg (=10)        with -l: the smallest length tried (10..1000, at most -k)\n"
                "  -t [ --atmost ] arg (=0)           with -l: a length is specific when its k-mer has at most this many places in the genome\n"
                "  -a [ --anchor ] arg                with -q: the last arg bases of every k-mer must match exactly (0..-k)\n"
+               "  -E [ --byend ]                     with -l: the length of the shortest specific k-mer that ENDS at the position; -a then 0..-s\n"
                "  -o [ --outfile ] arg               gzipped output file (default: plain text on stdout)\n"
                "\n"
                "Output: bedGraph lines name, start, end, value (0-based, end exclusive) of maximal runs of equal values, where the value\n"
@@ -64,7 +67,13 @@ void map_usage() {
                "With -q -a only the k-mers of the genome that match the LAST -a bases of the record's k-mer, the 3' end of the oligo, exactly\n"
                "are counted: the places a primer could extend from or a guide's seed could bind.  On the other strand the genome shows these\n"
                "bases, reverse-complemented, as the first -a of its k-mer.  -a 0 writes what -q alone writes, -a equal to -k what -e 0 writes.\n"
-               "-a cannot be combined with -l: with an anchored 3' end a longer oligo can have more places than a shorter one.\n"
+               "-a cannot be combined with -l unless -E is given: with an anchored 3' end a longer oligo can have more places than a shorter one.\n"
+               "With -q -l -E the value of a position of a record is the smallest length k (from -s to -k, inside the run of A/C/G/T that ends\n"
+               "there) at which the k-mer that ENDS at the position, the oligo whose 3' end it is, has at most -t places in the genome within\n"
+               "-e mismatches: how far a primer with this 3' end must reach back.  With -a (0..-s) only places that match the oligo's last -a\n"
+               "bases exactly are counted; the 3' end stays where it is while the oligo grows at its 5' end, so a longer oligo never has more\n"
+               "places.  The lines are at the coordinates of the oligo's LAST base; positions without such a length, and positions where not\n"
+               "even a k-mer of length -s ends, have no line.\n"
                "\n";
 }
 
@@ -123,9 +132,10 @@ bool read_fasta(const std::string& path, std::vector<std::string>& names, std::v
 }
 
 // bedGraph of the query records: one line per maximal run of equal values over valid positions, zero included.  With lp (-l) the values
-// are minimum lengths and zero, no length, has no line either; with ap (-a) they are the anchored counts
-int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_params* lp, const dg_qmap_anchor_params* ap, const std::string& query,
-                    const std::string& outfile) {
+// are minimum lengths and zero, no length, has no line either, and with ep (-l -E) those by end position, at the coordinates of the
+// k-mer's last base; with ap (-a) they are the anchored counts
+int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_params* lp, const dg_qminlen_end_params* ep,
+                    const dg_qmap_anchor_params* ap, const std::string& query, const std::string& outfile) {
   std::vector<std::string> names, seqs;
   if (!read_fasta(query, names, seqs)) return bail("Error: Could not read any sequence from " + query + "!");
   std::vector<uint64_t> off(seqs.size() + 1, 0);
@@ -134,7 +144,8 @@ int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_par
   all.reserve(off.back());
   for (const std::string& s : seqs) all += s;
   std::vector<uint32_t> val(off.back());
-  const int rc = lp   ? dg_query_min_len(ix, lp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
+  const int rc = ep   ? dg_query_min_len_end(ix, ep, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
+                 : lp ? dg_query_min_len(ix, lp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
                  : ap ? dg_query_map_anchored(ix, ap, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
                       : dg_query_map(ix, &qp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr);
   if (rc != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
@@ -170,7 +181,7 @@ int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_par
     for (uint64_t a = 0; a < len;) {
       uint64_t b = a + 1;
       while (b < len && v[b] == v[a]) ++b;
-      if (v[a] != DG_QMAP_INVALID && !(lp && v[a] == 0)) {
+      if (v[a] != DG_QMAP_INVALID && !((lp || ep) && v[a] == 0)) {
         text += names[i];
         text.push_back('\t');
         uint_append(text, a);
@@ -215,7 +226,7 @@ int mappability_main(int argc, char** argv) {
   }
   std::string genome, outfile, query;
   bool help = false, have_genome = false, forward = false, minunique = false, have_query = false, minlength = false, have_shortest = false,
-       have_atmost = false, have_anchor = false;
+       have_atmost = false, have_anchor = false, byend = false;
   long long k = 100, maxcount = 0, mismatches = 0, shortest = 10, atmost = 0, anchor = 0;
   for (auto& kv : p.kv) {
     if (kv.first == "help") help = true;
@@ -231,6 +242,7 @@ int mappability_main(int argc, char** argv) {
     else if (kv.first == "shortest") { shortest = std::strtoll(kv.second.c_str(), nullptr, 10); have_shortest = true; }
     else if (kv.first == "atmost") { atmost = std::strtoll(kv.second.c_str(), nullptr, 10); have_atmost = true; }
     else if (kv.first == "anchor") { anchor = std::strtoll(kv.second.c_str(), nullptr, 10); have_anchor = true; }
+    else if (kv.first == "byend") byend = true;
   }
   if (help || !have_genome || !p.positional.empty()) {
     map_usage();
@@ -248,10 +260,13 @@ int mappability_main(int argc, char** argv) {
   if (shortest > k) return bail("Error: shortest length " + std::to_string(shortest) + " above the largest length " + std::to_string(k) + " (-k)!");
   if (atmost < 0 || atmost > 0xFFFFFFFDll) return bail("Error: atmost " + std::to_string(atmost) + " outside 0..4294967293!");
   if (have_anchor && !have_query) return bail("Error: --anchor needs --query!");
-  if (have_anchor && minlength) return bail("Error: --anchor cannot be combined with --minlength!");
+  if (have_anchor && minlength && !byend) return bail("Error: --anchor cannot be combined with --minlength!");
   if (have_anchor && (anchor < 0 || anchor > k)) return bail("Error: anchor " + std::to_string(anchor) + " outside 0.." + std::to_string(k) + " (-k)!");
   if (!file_nonempty(genome)) return bail("Error: Genome does not exist!");
   if (have_query && !file_nonempty(query)) return bail("Error: Query file " + query + " does not exist or is empty!");
+  if (byend && !minlength) return bail("Error: --byend needs --minlength!");
+  if (byend && have_anchor && anchor > shortest)
+    return bail("Error: anchor " + std::to_string(anchor) + " above the shortest length " + std::to_string(shortest) + " (-s)!");
   std::vector<uint32_t> seqlen;
   std::vector<std::string> seqname;
   if (!seq_len_name(genome, seqlen, seqname)) return bail("Error: Could not retrieve sequence lengths!");
@@ -276,7 +291,9 @@ int mappability_main(int argc, char** argv) {
     const dg_qmap_params qp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, {0u, 0u, 0u}};
     const dg_qminlen_params lp = {(uint32_t)shortest, (uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)atmost, 0u, {0u, 0u}};
     const dg_qmap_anchor_params ap = {(uint32_t)k, (uint32_t)mismatches, (uint32_t)anchor, forward ? 1 : 0, (uint32_t)maxcount, 0u, {0u, 0u}};
-    return write_query_map(ix, qp, minlength ? &lp : nullptr, have_anchor ? &ap : nullptr, query, outfile);
+    const dg_qminlen_end_params ep = {(uint32_t)shortest, (uint32_t)k, (uint32_t)mismatches, (uint32_t)anchor, forward ? 1 : 0, (uint32_t)atmost, 0u,
+                                      {0u, 0u}};
+    return write_query_map(ix, qp, minlength && !byend ? &lp : nullptr, byend ? &ep : nullptr, have_anchor && !byend ? &ap : nullptr, query, outfile);
   }
   dg_map_mm_params mp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, 0u};
   dg_min_unique_params up = {(uint32_t)k, forward ? 1 : 0, 0u, 0u};

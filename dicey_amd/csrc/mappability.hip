@@ -18,7 +18,7 @@
 // dg_query_map (query_map.hpp) runs phase 1 on a buffer of query records laid out like the text and then one search per valid position
 // of it: the (k,e) counts of k-mers that are not in the index.  dg_query_min_len (query_min_len.hpp) looks, on the same buffer, for the
 // smallest k at which that count is at most t.  dg_query_map_anchored (query_anchor.hpp) is dg_query_map with the last a bases of every
-// k-mer matched exactly.
+// k-mer matched exactly.  dg_query_min_len_end (query_min_len_end.hpp) looks for the smallest k by the oligo's LAST base, anchored.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -210,6 +210,7 @@ __global__ void __launch_bounds__(256) k_heads(FmView f, u32 k, int forward_only
 #include "query_map.hpp"  // the same search per position of a query buffer (dg_query_map)
 #include "query_min_len.hpp"  // and the search for the smallest specific k per position (dg_query_min_len)
 #include "query_anchor.hpp"  // k_qmap with the k-mer's last bases matched exactly (dg_query_map_anchored)
+#include "query_min_len_end.hpp"  // the smallest specific k of the anchored k-mer that ENDS at a position (dg_query_min_len_end)
 namespace dg {
 
 // out[SA[i]] = the total of i's group (heads hold it in their own slot; members hold their head's rank), 0 for invalid ranks
@@ -684,14 +685,15 @@ static int query_map_impl(const char* who, dg_index* ix, const dg_qmap_params* p
   return DG_OK;
 }
 
-// the same buffer with the A/C/G/T bitmap alone (a lane finds its own limit), k_qminlen per chunk of positions
-static int query_min_len_impl(dg_index* ix, const dg_qminlen_params* prm, const std::vector<u8>& hq, std::vector<u32>& vals,
-                              dg_qminlen_stats_t* stt) {
+// the same buffer with the A/C/G/T bitmap alone (a lane finds its own limit), k_qminlen per chunk of positions.  anchor: null for
+// dg_query_min_len, else the lengths are by END position with that many last bases exact (k_qminlen_end): the same buffers, chunks and W
+static int query_min_len_impl(const char* who, dg_index* ix, const dg_qminlen_params* prm, const u32* anchor, const std::vector<u8>& hq,
+                              std::vector<u32>& vals, dg_qminlen_stats_t* stt) {
   const FmView& f = ix->view;
   const u64 qn = hq.size();
   hipStream_t st = ix->stream;
   QueryDev b(st);
-  DG_TRY(b.alloc("dg_query_min_len", qn, prm->max_k, 1, sizeof(QminlenCounters)));
+  DG_TRY(b.alloc(who, qn, prm->max_k, 1, sizeof(QminlenCounters)));
   u64 chunk = QMINLEN_CHUNK;
   u32 W = MM_NARROW;
   if (const char* e = exp_env("DICEY_QMINLEN_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
@@ -711,7 +713,17 @@ static int query_min_len_impl(dg_index* ix, const dg_qminlen_params* prm, const 
     const u64 p1 = std::min(qn, p0 + chunk);
     DG_TRY(tm.launch(st));
     const dim3 grid(ceil_div(p1 - p0, TB));
-    if (prm->mismatches == 0)
+    if (anchor) {
+      if (prm->mismatches == 0)
+        hipLaunchKernelGGL(k_qminlen_end<0>, grid, dim3(TB), 0, st, f, q, acgt, prm->min_k, prm->max_k, *anchor, prm->forward_only, W, prm->at_most, p0,
+                           p1, (u32*)b.out, ctr);
+      else if (prm->mismatches == 1)
+        hipLaunchKernelGGL(k_qminlen_end<1>, grid, dim3(TB), 0, st, f, q, acgt, prm->min_k, prm->max_k, *anchor, prm->forward_only, W, prm->at_most, p0,
+                           p1, (u32*)b.out, ctr);
+      else
+        hipLaunchKernelGGL(k_qminlen_end<2>, grid, dim3(TB), 0, st, f, q, acgt, prm->min_k, prm->max_k, *anchor, prm->forward_only, W, prm->at_most, p0,
+                           p1, (u32*)b.out, ctr);
+    } else if (prm->mismatches == 0)
       hipLaunchKernelGGL(k_qminlen<0>, grid, dim3(TB), 0, st, f, q, acgt, b.nw, prm->min_k, prm->max_k, prm->forward_only, W, prm->at_most, p0, p1,
                          (u32*)b.out, ctr);
     else if (prm->mismatches == 1)
@@ -741,7 +753,10 @@ static int query_min_len_impl(dg_index* ix, const dg_qminlen_params* prm, const 
   stt->ms_valid = ms[0];
   stt->ms_search = ms[1];
   stt->ms_total = (double)ms[0] + (double)ms[1];  // in double: exactly the sum of the reported parts
-  if (tm.timing && launches)
+  if (tm.timing && launches && anchor)
+    std::fprintf(stderr, "dicey timing: query min length by end e=%u anchor=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n",
+                 prm->mismatches, *anchor, (unsigned long long)launches, ms[1], longest);
+  else if (tm.timing && launches)
     std::fprintf(stderr, "dicey timing: query min length e=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n", prm->mismatches,
                  (unsigned long long)launches, ms[1], longest);
   return DG_OK;
@@ -866,7 +881,33 @@ int dg_query_min_len(dg_index* ix, const dg_qminlen_params* p, const uint8_t* se
     DG_HIP(hipSetDevice(ix->device));
     const std::vector<u8> hq = query_pack(seqs, off, nseq);
     std::vector<u32> vals(hq.size());
-    DG_TRY(query_min_len_impl(ix, p, hq, vals, &st));
+    DG_TRY(query_min_len_impl("dg_query_min_len", ix, p, nullptr, hq, vals, &st));
+    query_unpack(vals, off, nseq, values);
+  }
+  if (stats) *stats = st;
+  return DG_OK;
+}
+
+int dg_query_min_len_end(dg_index* ix, const dg_qminlen_end_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
+                         dg_qminlen_stats_t* stats) {
+  if (!p) return fail(DG_EINVAL, "dg_query_min_len_end: null argument");
+  if (p->flags || p->reserved[0] || p->reserved[1]) return fail(DG_EINVAL, "dg_query_min_len_end: flags and reserved must be 0");
+  if (p->min_k < 10 || p->min_k > 1000) return fail(DG_ELIMIT, "dg_query_min_len_end: min_k = %u outside 10..1000", p->min_k);
+  if (p->max_k < 10 || p->max_k > 1000) return fail(DG_ELIMIT, "dg_query_min_len_end: max_k = %u outside 10..1000", p->max_k);
+  if (p->min_k > p->max_k) return fail(DG_ELIMIT, "dg_query_min_len_end: min_k = %u above max_k = %u", p->min_k, p->max_k);
+  if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_query_min_len_end: %u mismatches outside 0..2", p->mismatches);
+  if (p->at_most > 0xFFFFFFFDu) return fail(DG_ELIMIT, "dg_query_min_len_end: at_most = %u above 4294967293", p->at_most);
+  if (p->anchor > p->min_k) return fail(DG_ELIMIT, "dg_query_min_len_end: anchor = %u above min_k = %u", p->anchor, p->min_k);
+  DG_TRY(query_args_check("dg_query_min_len_end", ix, seqs, off, nseq, values, true));
+  const u64 total = (off && nseq) ? off[nseq] : 0;
+  dg_qminlen_stats_t st{};
+  st.positions = nseq ? total - off[0] : 0;
+  if (total) {
+    DG_HIP(hipSetDevice(ix->device));
+    const dg_qminlen_params q = {p->min_k, p->max_k, p->mismatches, p->forward_only, p->at_most, 0u, {0u, 0u}};
+    const std::vector<u8> hq = query_pack(seqs, off, nseq);
+    std::vector<u32> vals(hq.size());
+    DG_TRY(query_min_len_impl("dg_query_min_len_end", ix, &q, &p->anchor, hq, vals, &st));
     query_unpack(vals, off, nseq, values);
   }
   if (stats) *stats = st;

@@ -625,7 +625,8 @@ int dg_query_min_len(dg_index* ix, const dg_qminlen_params* p, const uint8_t* se
  * The anchored bases are always the last a of the oligo w; on the other strand the text shows them as the FIRST a bases of the window.
  * anchor = 0 gives dg_query_map's values, anchor = k its e = 0 values, and the value never rises with the anchor.  It is NOT monotone
  * in k for an oligo that grows at its 3' end (a site whose only mismatch is at offset k-1 is rejected at length k and accepted at
- * k+1), so dg_query_min_len has no anchor.
+ * k+1), so dg_query_min_len has no anchor.  By END position, the 3' end fixed and the oligo growing at its 5' end, it is monotone:
+ * dg_query_min_len_end below.
  * Checks, in this order: a null block, non-zero flags or reserved DG_EINVAL; k outside 10..1000, mismatches > 2 or anchor > k DG_ELIMIT;
  * off[nseq] + nseq >= 2^31 DG_ELIMIT; no device DG_ENODEV; a null handle, null seqs / off / values (where there is something to read or
  * write) or decreasing offsets DG_EINVAL; then DG_EINVAL while a dg_hunt_submit batch is in flight on the handle.  On every failure
@@ -641,6 +642,39 @@ typedef struct {
 } dg_qmap_anchor_params;
 int dg_query_map_anchored(dg_index* ix, const dg_qmap_anchor_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
                           dg_qmap_stats_t* stats /* may be NULL */);
+
+/* ABI 7, additive.  Query minimum length by END position: how far must an oligo whose 3' end is position p of a record reach back before
+ * at most `at_most` places of the genome are within `mismatches` substitutions of it with its last `anchor` bases exact?  The question of
+ * a primer (its 3' end), a padlock arm (its ligation junction) or a guide (its PAM-proximal end) slid along a target.  Records, bytes,
+ * DG_QMAP_INVALID, forward_only and the layout of `values` are dg_query_min_len's: one uint32 per byte of every record, here at the index
+ * of the oligo's LAST base.  For a record Q and a position p:
+ *   brun(p)    = the number of consecutive A/C/G/T bytes of Q that end at p, p included (0 when Q[p] is none; the record's start ends a
+ *                run),   limit(p) = min(brun(p), max_k),
+ *   w_k        = Q[p-k+1, p+1) for k <= limit(p),
+ *   value_k(p) = what dg_query_map_anchored returns at position p-k+1 for this k, mismatches, anchor and forward_only with max_count = 0,
+ *   len(p)     = DG_QMAP_INVALID when limit(p) < min_k, otherwise the smallest k in [min_k, limit(p)] with value_k(p) <= at_most, and 0
+ *                when there is none.
+ * anchor <= min_k, so the anchored bases are the same bases Q[p-a+1, p] at every length tried; anchor = 0 is the unanchored minimum
+ * length by end position.  value_k(p) never rises with k (w_{k+1} = x w_k: a window within e of w_{k+1} whose last a bases are exact has
+ * its k-suffix within e of w_k with the same exact bases, one position to the right; on the other strand its k-prefix, at the same
+ * start), so the device searches per position: one call where a scan of dg_query_map_anchored needs max_k - min_k + 1.  A non-zero len
+ * never grows with the anchor.  Stream, chunks and memory as dg_query_min_len.  nseq = 0 succeeds and writes nothing.  Checked in this
+ * order: a null parameter block, non-zero flags or reserved DG_EINVAL; min_k or max_k outside 10..1000, min_k > max_k, mismatches > 2,
+ * at_most > 0xFFFFFFFD or anchor > min_k DG_ELIMIT; off[nseq] + nseq >= 2^31 DG_ELIMIT; no usable HIP device DG_ENODEV; a null handle,
+ * null seqs / off / values (where there is something to read or write) or decreasing offsets DG_EINVAL; then DG_EINVAL while a
+ * dg_hunt_submit batch is in flight on the handle.  On every failure `values` is left untouched. */
+typedef struct {
+  uint32_t min_k;       /* smallest length tried, 10..1000 */
+  uint32_t max_k;       /* largest length tried, min_k..1000 */
+  uint32_t mismatches;  /* e: 0, 1 or 2 substitutions */
+  uint32_t anchor;      /* a: the last a bases of the oligo match exactly, 0..min_k */
+  int32_t forward_only; /* count the oligo alone, not its reverse complement */
+  uint32_t at_most;     /* t: a length is specific when its value is <= t; 0..0xFFFFFFFD */
+  uint32_t flags;       /* 0 */
+  uint32_t reserved[2]; /* 0 */
+} dg_qminlen_end_params;
+int dg_query_min_len_end(dg_index* ix, const dg_qminlen_end_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
+                         dg_qminlen_stats_t* stats /* may be NULL */);
 
 const char* dg_last_error(void);
 int dg_abi_version(void);

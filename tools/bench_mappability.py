@@ -15,7 +15,9 @@ dg_query_map_anchored (the last A bases of every k-mer matched exactly; `k` stan
 With --query-minlen [--mismatches e] [--atmost t[,t..]] [--mink a --maxk b] [--no-scan] the same query
 set goes through dg_query_min_len (the shortest specific k-mer per position), one warm-up call in front of the timed one: device and wall
 ms, probes per valid position, the longest launch -- and beside it the route a build without it offers: one dg_query_map(k, max_count =
-t + 1) per k in [a, b], combined on the host; `same_values` compares the two.  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
+t + 1) per k in [a, b], combined on the host; `same_values` compares the two.  With --query-minlen --by-end [--anchor A[,A..]] the call is
+dg_query_min_len_end (the shortest specific k-mer that ENDS at each position, its last A bases exact) and the scan beside it one
+dg_query_map_anchored(k, A, max_count = t + 1) per k, each result shifted by k - 1 to the k-mer's last base on the host.  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
 Prints one JSON line."""
 import argparse, ctypes as C, json, os, re, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,6 +39,8 @@ ap.add_argument("--query-mb", type=float, default=1.0, help="Mb of each half of 
 ap.add_argument("--anchor", default="", help="with --query: time dg_query_map_anchored at these anchors (comma-separated; k = the k-mer length) beside "
                 "dg_query_map at the same k and e (e = 1, 2, or --mismatches when given)")
 ap.add_argument("--query-minlen", action="store_true", help="time dg_query_min_len (--mink..--maxk, --mismatches, --atmost) beside a per-k scan of dg_query_map")
+ap.add_argument("--by-end", action="store_true", help="--query-minlen: time dg_query_min_len_end (anchors of --anchor, default 0) beside a per-k scan "
+                "of dg_query_map_anchored shifted to the k-mer's last base")
 ap.add_argument("--mink", type=int, default=10, help="min_k of --query-minlen")
 ap.add_argument("--atmost", default="0", help="at_most of --query-minlen; a comma-separated list gives one run each")
 ap.add_argument("--no-scan", action="store_true", help="--query-minlen: skip the per-k scan of dg_query_map beside the call")
@@ -48,6 +52,8 @@ ap.add_argument("--workdir", default="/dev/shm")
 a = ap.parse_args()
 if a.min_unique and (a.mismatches or a.maxcount):
     ap.error("--min-unique goes with neither --mismatches nor --maxcount")
+if a.by_end and not a.query_minlen:
+    ap.error("--by-end goes with --query-minlen")
 dev = torch.device("cuda", 0)
 L = _capi.load()
 out = {"tool": "bench_mappability", "genome": a.genome, "genome_size": a.genome_size}
@@ -275,9 +281,69 @@ def query_minlen_run(recs, t):
     return run
 
 
+def query_minlen_end_run(recs, t, anc):
+    import numpy as np
+    buf = b"".join(recs)
+    off = np.zeros(len(recs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(r) for r in recs])
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    offp = off.ctypes.data_as(u64p)
+    INV = _capi.DG_QMAP_INVALID
+    e = a.mismatches
+    got = np.zeros(len(buf), dtype=np.uint32)
+    prm = _capi.QminlenEndParams(a.mink, a.maxk, e, anc, 0, t, 0, (C.c_uint32 * 2)(0, 0))
+    st = _capi.QminlenStats()
+    _capi.check(L, L.dg_query_min_len_end(ix.handle, C.byref(prm), buf, offp, len(recs), got.ctypes.data_as(u32p), None))  # (warm-up)
+    os.environ["DICEY_TIMING"] = "1"
+    t0 = time.time()
+    err = stderr_of(lambda: _capi.check(L, L.dg_query_min_len_end(ix.handle, C.byref(prm), buf, offp, len(recs), got.ctypes.data_as(u32p), C.byref(st))))
+    wall = time.time() - t0
+    del os.environ["DICEY_TIMING"]
+    line = re.search(r"query min length by end e=\d+ anchor=\d+: (\d+) launches of the search, [0-9.]+ ms in all, longest ([0-9.]+) ms", err)
+    v = max(st.valid, 1)
+    run = {"query_minlen_end": True, "min_k": a.mink, "max_k": a.maxk, "mismatches": e, "anchor": anc, "at_most": t, "positions": st.positions,
+           "valid": st.valid, "found": st.found, "wall_ms": round(wall * 1e3, 2), "ms_total": round(st.ms_total, 2), "ms_valid": round(st.ms_valid, 2),
+           "ms_search": round(st.ms_search, 2), "launches": st.launches, "longest_launch_ms": float(line.group(2)) if line else None,
+           "probes_per_position": round(st.probes / v, 2), "steps_per_position": round(st.steps / v, 2),
+           "table_reads_per_position": round(st.table_reads / v, 2), "verified_rows_per_position": round(st.verified_rows / v, 2)}
+    if a.no_scan:
+        return run
+    # the route without dg_query_min_len_end: one dg_query_map_anchored per k with max_count = t + 1, every result shifted by k - 1 to the
+    # k-mer's last base inside its record, the first k with a value <= t taken on the host
+    vals = np.zeros(len(buf), dtype=np.uint32)
+    rec_of = np.repeat(np.arange(len(recs)), [len(r) for r in recs])
+    in_rec = np.arange(len(buf)) - off[:-1].astype(np.int64)[rec_of]
+    qp = _capi.QmapAnchorParams(a.mink, e, anc, 0, t + 1, 0, (C.c_uint32 * 2)(0, 0))
+    _capi.check(L, L.dg_query_map_anchored(ix.handle, C.byref(qp), buf, offp, 1, vals.ctypes.data_as(u32p), None))  # (warm-up: one record)
+    scan = None
+    dev_ms = 0.0
+    t0 = time.time()
+    for k in range(a.mink, a.maxk + 1):
+        qp = _capi.QmapAnchorParams(k, e, anc, 0, t + 1, 0, (C.c_uint32 * 2)(0, 0))
+        qs = _capi.QmapStats()
+        _capi.check(L, L.dg_query_map_anchored(ix.handle, C.byref(qp), buf, offp, len(recs), vals.ctypes.data_as(u32p), C.byref(qs)))
+        dev_ms += qs.ms_total
+        end = np.full(len(buf), INV, dtype=np.uint32)
+        end[k - 1:] = vals[:len(buf) - k + 1]
+        end[in_rec < k - 1] = INV  # (a value shifted in from the record in front)
+        if scan is None:
+            scan = np.where(end == INV, INV, 0).astype(np.uint32)
+        scan[(scan == 0) & (end != INV) & (end <= t)] = k
+    scan_wall = time.time() - t0
+    run.update({"scan_calls": a.maxk - a.mink + 1, "scan_wall_ms": round(scan_wall * 1e3, 2), "scan_ms_total": round(dev_ms, 2),
+                "same_values": bool((scan == got).all()), "scan_over_call_wall": round(scan_wall / max(wall, 1e-9), 2),
+                "scan_over_call_device": round(dev_ms / max(st.ms_total, 1e-9), 2)})
+    return run
+
+
 if a.query_minlen:
     recs = query_set()
     for t in [int(x) for x in a.atmost.split(",")]:
+        if a.by_end:
+            for anc in [int(x) for x in (a.anchor or "0").split(",")]:
+                runs.append(query_minlen_end_run(recs, t, anc))
+                print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+            continue
         runs.append(query_minlen_run(recs, t))
         print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
     ks = []
