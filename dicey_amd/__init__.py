@@ -226,6 +226,18 @@ class FmIndex:
         finally:
             self._L.dg_map_free(m)
 
+    def _query(self, fn, prm, st, seqs, stats):
+        """One dg_query_* call: upper-case and pack the records, call `fn` with the parameter block `prm`, copy the stats struct `st`
+        into `stats` and split the values per record."""
+        import numpy as np
+        recs = [s.upper().encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        buf, off = _pack(recs)
+        out = np.zeros(len(buf), dtype=np.uint32)
+        _capi.check(self._L, fn(self._h, C.byref(prm), buf, off, len(recs), out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st)))
+        if stats is not None:
+            stats.update({f: getattr(st, f) for f, _ in st._fields_})
+        return [out[off[i]:off[i + 1]].copy() for i in range(len(recs))]
+
     def query_mappability(self, seqs: Sequence, k: int = 100, forward_only: bool = False, max_count: int = 0, mismatches: int = 0,
                           stats: Optional[dict] = None, anchor: Optional[int] = None):
         """k-mer counts for sequences that are NOT in the index (include/dicey_gpu.h dg_query_map): a list with one numpy uint32 array
@@ -235,21 +247,11 @@ class FmIndex:
         bytes go through as given.  `stats`, when given, receives dg_qmap_stats_t.  With `anchor` = a (0..k; dg_query_map_anchored) only
         windows that match the LAST a bases of w, the oligo's 3' end, exactly are counted; on the other strand these are the first a
         bases of the window.  None calls dg_query_map."""
-        import numpy as np
-        recs = [s.upper().encode() if isinstance(s, str) else bytes(s) for s in seqs]
-        buf, off = _pack(recs)
-        out = np.zeros(len(buf), dtype=np.uint32)
-        st = _capi.QmapStats()
-        outp = out.ctypes.data_as(C.POINTER(C.c_uint32))
         if anchor is None:
             prm = _capi.QmapParams(k, mismatches, 1 if forward_only else 0, max_count, 0, (C.c_uint32 * 3)(0, 0, 0))
-            _capi.check(self._L, self._L.dg_query_map(self._h, C.byref(prm), buf, off, len(recs), outp, C.byref(st)))
-        else:
-            prm = _capi.QmapAnchorParams(k, mismatches, anchor, 1 if forward_only else 0, max_count, 0, (C.c_uint32 * 2)(0, 0))
-            _capi.check(self._L, self._L.dg_query_map_anchored(self._h, C.byref(prm), buf, off, len(recs), outp, C.byref(st)))
-        if stats is not None:
-            stats.update({f: getattr(st, f) for f, _ in _capi.QmapStats._fields_})
-        return [out[off[i]:off[i + 1]].copy() for i in range(len(recs))]
+            return self._query(self._L.dg_query_map, prm, _capi.QmapStats(), seqs, stats)
+        prm = _capi.QmapAnchorParams(k, mismatches, anchor, 1 if forward_only else 0, max_count, 0, (C.c_uint32 * 2)(0, 0))
+        return self._query(self._L.dg_query_map_anchored, prm, _capi.QmapStats(), seqs, stats)
 
     def query_min_length(self, seqs: Sequence, max_k: int = 100, min_k: int = 10, at_most: int = 0, mismatches: int = 0,
                          forward_only: bool = False, stats: Optional[dict] = None):
@@ -258,17 +260,8 @@ class FmIndex:
         query_mappability(k, mismatches, forward_only) is at most `at_most` at p (0: absent from the genome; 1: at most one place);
         0 = no such length; QMAP_INVALID where not even a min_k-mer of A/C/G/T starts.  str records are upper-cased, bytes go through
         as given.  `stats`, when given, receives dg_qminlen_stats_t."""
-        import numpy as np
-        recs = [s.upper().encode() if isinstance(s, str) else bytes(s) for s in seqs]
-        buf, off = _pack(recs)
-        out = np.zeros(len(buf), dtype=np.uint32)
         prm = _capi.QminlenParams(min_k, max_k, mismatches, 1 if forward_only else 0, at_most, 0, (C.c_uint32 * 2)(0, 0))
-        st = _capi.QminlenStats()
-        _capi.check(self._L, self._L.dg_query_min_len(self._h, C.byref(prm), buf, off, len(recs), out.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                      C.byref(st)))
-        if stats is not None:
-            stats.update({f: getattr(st, f) for f, _ in _capi.QminlenStats._fields_})
-        return [out[off[i]:off[i + 1]].copy() for i in range(len(recs))]
+        return self._query(self._L.dg_query_min_len, prm, _capi.QminlenStats(), seqs, stats)
 
     def query_min_length_end(self, seqs: Sequence, max_k: int = 100, min_k: int = 10, at_most: int = 0, mismatches: int = 0,
                              anchor: int = 0, forward_only: bool = False, stats: Optional[dict] = None):
@@ -278,17 +271,8 @@ class FmIndex:
         within `mismatches` substitutions and with its last `anchor` bases (0..min_k) exact, i.e. at which
         query_mappability(k, anchor=anchor)[p - k + 1] <= at_most; 0 = no such length; QMAP_INVALID where not even a min_k-mer of
         A/C/G/T ends.  str records are upper-cased, bytes go through as given.  `stats`, when given, receives dg_qminlen_stats_t."""
-        import numpy as np
-        recs = [s.upper().encode() if isinstance(s, str) else bytes(s) for s in seqs]
-        buf, off = _pack(recs)
-        out = np.zeros(len(buf), dtype=np.uint32)
         prm = _capi.QminlenEndParams(min_k, max_k, mismatches, anchor, 1 if forward_only else 0, at_most, 0, (C.c_uint32 * 2)(0, 0))
-        st = _capi.QminlenStats()
-        _capi.check(self._L, self._L.dg_query_min_len_end(self._h, C.byref(prm), buf, off, len(recs),
-                                                          out.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(st)))
-        if stats is not None:
-            stats.update({f: getattr(st, f) for f, _ in _capi.QminlenStats._fields_})
-        return [out[off[i]:off[i + 1]].copy() for i in range(len(recs))]
+        return self._query(self._L.dg_query_min_len_end, prm, _capi.QminlenStats(), seqs, stats)
 
     def _map_runs(self, m, lo, hi):
         import numpy as np

@@ -12,9 +12,13 @@
 //   narrow   an interval of at most W rows is finished on the text: the remaining characters in front of SA[r] against the rest of the
 //            pattern, 8 bytes at a time, with the remaining budget.  A mismatching byte outside A/C/G/T (N, IUPAC, '\n') or a start
 //            before position 0 rejects the row.  On a mostly unique genome that ends the search right behind the table, whatever k is.
-// Included by mappability.hip behind text8 / acgt_code / bit_at.
+// Anchored (dg_query_map_anchored, query_anchor.hpp): the same search on an AnchLane, whose steps [t0, t1) must show the pattern's own
+// character.  Lane::anchored is a compile-time trait, and every anchored condition below is written `Lane::anchored && ...` or as an
+// `if constexpr`: on an MmLane the front end then drops it before anything is inlined.  A helper that merely returns false there is folded
+// later and moves blocks of the e >= 1 kernels (DESIGN.md §10 has the instruction counts).  The kernels set the lane up with mm_lane_init
+// and mm_set_strand and flush it with mm_flush; the strand loop itself stays in each kernel (§10 again).
 #pragma once
-#include "devfm.hpp"
+#include "text_bits.hpp"
 
 namespace dg {
 
@@ -23,6 +27,7 @@ struct MmCounters {  // device record, one wave_add per field and wavefront
 };
 
 struct MmLane {  // one lane's search of one k-mer w: its constants and the running results
+  static constexpr bool anchored = false;
   const u8* pat;  // the buffer w is read from: the text for a group head, the query buffer for k_qmap (query_map.hpp).  8-byte reads of
                   // it touch only the aligned words that overlap [p, p + k + 8): never in front of an 8-aligned buffer, and behind its
                   // last k-mer inside the text's slack.  Windows are always read from f.text
@@ -34,6 +39,27 @@ struct MmLane {  // one lane's search of one k-mer w: its constants and the runn
   u64 total;  // both strands
   u32 steps, tab, rows;
 };
+
+struct AnchLane : MmLane {  // and the steps of the current strand at which the text must show the pattern's own character
+  static constexpr bool anchored = true;
+  u32 t0, t1;
+};
+
+// step t is anchored: no substitution there (never on a plain lane; callers write `Lane::anchored &&` in front, see the header)
+template <class Lane>
+DG_DEV bool mm_fixed_step(const Lane& c, u32 t) {
+  if constexpr (Lane::anchored) return t >= c.t0 && t < c.t1;
+  else return false;
+}
+
+// 0xFF in every byte b of the word at pattern index j whose index j + b lies in [i0, i1)
+DG_DEV u64 anch_byte_mask(u32 j, u32 i0, u32 i1) {
+  const u32 s = i0 > j ? i0 - j : 0u;
+  const u32 e = i1 > j ? (i1 - j < 8u ? i1 - j : 8u) : 0u;
+  if (s >= e) return 0;  // (so s <= 7)
+  const u64 below_e = e == 8u ? ~0ULL : (1ULL << (8 * e)) - 1;
+  return below_e & ~((1ULL << (8 * s)) - 1);
+}
 
 // the pattern's character met at backward-search step t (its LAST character at t = 0), as a code 0..3.  revcomp(w) from its last
 // character to its first is w from its first to its last, complemented.
@@ -68,9 +94,13 @@ DG_DEV u64 mm_pat8(const FmView& f, const MmLane& c, u32 m, u32 j) {
 }
 
 // rows [lo, hi) hold the suffixes that start with the t characters consumed so far: count those whose k - t characters in front spell
-// the rest of the pattern with at most `budget` substitutions
-DG_DEV void mm_verify(const FmView& f, MmLane& c, u32 t, u32 lo, u32 hi, u32 budget) {
+// the rest of the pattern with at most `budget` substitutions.  Anchored: a mismatching byte whose pattern index lies in the anchored
+// range [k - t1, k - t0) rejects the row, as a byte outside A/C/G/T does
+template <class Lane>
+DG_DEV void mm_verify(const FmView& f, Lane& c, u32 t, u32 lo, u32 hi, u32 budget) {
   const u32 m = c.k - t;
+  [[maybe_unused]] u32 i0 = 0, i1 = 0;  // the anchored index range
+  if constexpr (Lane::anchored) i0 = c.k - c.t1, i1 = c.k - c.t0;
   for (u32 r = lo; r < hi; ++r) {
     if (c.cap && c.total >= c.cap) return;
     const u64 s = f.sa[r];
@@ -86,7 +116,9 @@ DG_DEV void mm_verify(const FmView& f, MmLane& c, u32 t, u32 lo, u32 hi, u32 bud
       const u64 nz = mm_nonzero_bytes(x);
       if (nz) {
         mism += (u32)__popcll(nz);
-        ok = mism <= budget && (nz & ~mm_acgt_bytes(y)) == 0;
+        // (both forms leave the byte masks behind the budget test: they are formed only while the row is still within budget)
+        if constexpr (Lane::anchored) ok = mism <= budget && (nz & (~mm_acgt_bytes(y) | anch_byte_mask(j, i0, i1))) == 0;
+        else ok = mism <= budget && (nz & ~mm_acgt_bytes(y)) == 0;
       }
     }
     c.total += ok;
@@ -94,8 +126,9 @@ DG_DEV void mm_verify(const FmView& f, MmLane& c, u32 t, u32 lo, u32 hi, u32 bud
 }
 
 // the string whose last t characters have the interval [lo, hi), extended to the pattern's full length with at most B substitutions
-template <int B>
-DG_DEV void mm_search(const FmView& f, MmLane& c, u32 t, u32 lo, u32 hi) {
+// (no sibling is spawned at an anchored step)
+template <int B, class Lane>
+DG_DEV void mm_search(const FmView& f, Lane& c, u32 t, u32 lo, u32 hi) {
   while (t < c.k && lo < hi) {
     if (c.cap && c.total >= c.cap) return;
     if (hi - lo <= c.W) {
@@ -114,10 +147,12 @@ DG_DEV void mm_search(const FmView& f, MmLane& c, u32 t, u32 lo, u32 hi) {
     ++c.steps;
     const u32 pc = mm_pat_code(f, c, t);
     if constexpr (B > 0) {
-      for (u32 d = 1; d < 4; ++d) {  // the sibling counter of this level
-        const u32 a = (pc + d) & 3u;
-        const u32 l = sel4(a, nlo[0], nlo[1], nlo[2], nlo[3]), h = sel4(a, nhi[0], nhi[1], nhi[2], nhi[3]);
-        if (l < h) mm_search<B - 1>(f, c, t + 1, l, h);
+      if (!(Lane::anchored && mm_fixed_step(c, t))) {
+        for (u32 d = 1; d < 4; ++d) {  // the sibling counter of this level
+          const u32 a = (pc + d) & 3u;
+          const u32 l = sel4(a, nlo[0], nlo[1], nlo[2], nlo[3]), h = sel4(a, nhi[0], nhi[1], nhi[2], nhi[3]);
+          if (l < h) mm_search<B - 1>(f, c, t + 1, l, h);
+        }
       }
     }
     lo = sel4(pc, nlo[0], nlo[1], nlo[2], nlo[3]);
@@ -127,9 +162,9 @@ DG_DEV void mm_search(const FmView& f, MmLane& c, u32 t, u32 lo, u32 hi) {
   if (lo < hi) c.total += hi - lo;
 }
 
-// one strand of one head: the table start, then the levels
-template <int E>
-DG_DEV void mm_strand(const FmView& f, MmLane& c) {
+// one strand of one head: the table start (substitutions at its free steps only), then the levels
+template <int E, class Lane>
+DG_DEV void mm_strand(const FmView& f, Lane& c) {
   if (!(f.K && c.k >= f.K)) {
     mm_search<E>(f, c, 0, 0, (u32)f.n);
     return;
@@ -143,7 +178,8 @@ DG_DEV void mm_strand(const FmView& f, MmLane& c) {
     if (e0.lo < e0.hi) mm_search<E>(f, c, K, e0.lo, e0.hi);
   }
   if constexpr (E >= 1) {
-    for (u32 i = 0; i < K; ++i)
+    for (u32 i = 0; i < K; ++i) {
+      if (Lane::anchored && mm_fixed_step(c, i)) continue;
       for (u64 a = 1; a < 4; ++a) {
         if (c.cap && c.total >= c.cap) return;
         const u64 code1 = code ^ (a << (2 * i));
@@ -151,16 +187,52 @@ DG_DEV void mm_strand(const FmView& f, MmLane& c) {
         ++c.tab;
         if (e1.lo < e1.hi) mm_search<E - 1>(f, c, K, e1.lo, e1.hi);
         if constexpr (E >= 2) {
-          for (u32 j = 0; j < i; ++j)
+          for (u32 j = 0; j < i; ++j) {
+            if (Lane::anchored && mm_fixed_step(c, j)) continue;
             for (u64 b = 1; b < 4; ++b) {
               if (c.cap && c.total >= c.cap) return;
               const KtabEntry e2 = ktab_entry(f, code1 ^ (b << (2 * j)));
               ++c.tab;
               if (e2.lo < e2.hi) mm_search<E - 2>(f, c, K, e2.lo, e2.hi);
             }
+          }
         }
       }
+    }
   }
+}
+
+// a lane at position p of `pat` with nothing counted yet
+template <class Lane>
+DG_DEV void mm_lane_init(Lane& c, const u8* pat, u64 p, u32 k, u32 W, u32 cap) {
+  c.pat = pat;
+  c.p = p;
+  c.k = k;
+  c.rev = false;
+  c.W = W;
+  c.cap = cap;
+  c.total = 0;
+  c.steps = c.tab = c.rows = 0;
+  if constexpr (Lane::anchored) c.t0 = c.t1 = 0;
+}
+
+// the lane's next mm_strand is of its k-mer w or, with rev, of revcomp(w).  On an anchored lane the last `anchor` bases of w are exact:
+// step t consumes pattern index k-1-t, so they are the steps [0, anchor) of w and, being revcomp(w)'s first bases, its steps [k - anchor, k)
+template <class Lane>
+DG_DEV void mm_set_strand(Lane& c, bool rev, u32 anchor = 0) {
+  c.rev = rev;
+  if constexpr (Lane::anchored) {
+    c.t0 = rev ? c.k - anchor : 0u;
+    c.t1 = rev ? c.k : anchor;
+  }
+}
+
+// the lane's search counters into a device record (every lane of the wavefront must be here)
+template <class Counters>
+DG_DEV void mm_flush(Counters* ctr, const MmLane& c) {
+  wave_add(&ctr->steps, c.steps);
+  wave_add(&ctr->table_reads, c.tab);
+  wave_add(&ctr->verified_rows, c.rows);
 }
 
 // ranks [r0, r1): every group head among them gets the saturated total of its k-mer in its slot of `start`
@@ -169,14 +241,7 @@ __global__ void __launch_bounds__(256) k_heads_mm(FmView f, u32 k, int forward_o
                                                  MmCounters* ctr) {
   const u64 i = r0 + (u64)blockIdx.x * blockDim.x + threadIdx.x;
   MmLane c;
-  c.pat = f.text;
-  c.p = 0;
-  c.k = k;
-  c.rev = false;
-  c.W = W;
-  c.cap = cap;
-  c.total = 0;
-  c.steps = c.tab = c.rows = 0;
+  mm_lane_init(c, f.text, 0, k, W, cap);
   u32 head = 0, early = 0;
   if (i < r1 && bit_at(hd, i)) {
     head = 1;
@@ -184,16 +249,14 @@ __global__ void __launch_bounds__(256) k_heads_mm(FmView f, u32 k, int forward_o
     const u32 strands = forward_only ? 1u : 2u;
 #pragma nounroll
     for (u32 s = 0; s < strands && !(cap && c.total >= cap); ++s) {  // (a loop: one copy of the search in the kernel)
-      c.rev = s != 0;
+      mm_set_strand(c, s != 0);
       mm_strand<E>(f, c);
     }
     early = cap && c.total >= cap;
     start[i] = c.total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)c.total;
   }
   wave_add(&ctr->heads, head);  // (every lane of the wavefront is here)
-  wave_add(&ctr->steps, c.steps);
-  wave_add(&ctr->table_reads, c.tab);
-  wave_add(&ctr->verified_rows, c.rows);
+  mm_flush(ctr, c);
   wave_add(&ctr->early_exits, early);
 }
 

@@ -25,12 +25,21 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
-
+#include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "devfm.hpp"
 #include "experiments.hpp"
 #include "index_internal.hpp"
+#include "map_mm.hpp"           // k_heads' sibling for e >= 1 mismatches
+#include "min_unique.hpp"         // the kernels of dg_min_unique
+#include "query_anchor.hpp"       // k_qmap with the k-mer's last bases matched exactly (dg_query_map_anchored)
+#include "query_map.hpp"          // the same search per position of a query buffer (dg_query_map)
+#include "query_min_len.hpp"      // and the search for the smallest specific k per position (dg_query_min_len)
+#include "query_min_len_end.hpp"  // the smallest specific k of the anchored k-mer that ENDS at a position (dg_query_min_len_end)
+#include "text_bits.hpp"          // text8, acgt_code, the A/C/G/T and valid bitmaps
 
 struct dg_map {
   int device = 0;
@@ -56,76 +65,6 @@ struct dg_map {
 };
 
 namespace dg {
-
-__host__ __device__ inline bool bit_at(const u64* b, u64 i) { return (b[i >> 6] >> (i & 63)) & 1ULL; }
-
-// 8 text bytes from any position (little endian: byte p in bits 0-7); the text buffer has 64 bytes of slack behind n
-DG_DEV u64 text8(const u8* t, u64 p) {
-  const u64* w = reinterpret_cast<const u64*>(t + (p & ~7ULL));
-  const u32 s = (u32)(p & 7) * 8;
-  const u64 lo = w[0];
-  return s ? (lo >> s) | (w[1] << (64 - s)) : lo;
-}
-// 2-bit code of an A/C/G/T byte: A 0x41 -> 0, C 0x43 -> 1, G 0x47 -> 2, T 0x54 -> 3
-DG_DEV u32 acgt_code(u32 b) { return ((b >> 1) ^ (b >> 2)) & 3u; }
-
-// bit j of word w = T[64w + j] is A/C/G/T (positions >= n, the sentinel and the padding words are 0)
-__global__ void k_acgt_bits(const u8* text, u64 n, u64* acgt, u64 nw) {
-  const u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= nw) return;
-  u64 m = 0;
-  const u64 p0 = w * 64;
-  if (p0 < n) {
-    const uint4* q = reinterpret_cast<const uint4*>(text + p0);
-#pragma unroll
-    for (u32 c = 0; c < 4; ++c) {
-      const uint4 v = q[c];
-      const u32 wd[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (u32 j = 0; j < 16; ++j) {
-        const u32 b = (wd[j >> 2] >> (8 * (j & 3))) & 255u;
-        const bool ok = b == 'A' || b == 'C' || b == 'G' || b == 'T';
-        m |= (u64)ok << (c * 16 + j);
-      }
-    }
-    if (n - p0 < 64) m &= (1ULL << (n - p0)) - 1;
-  }
-  acgt[w] = m;
-}
-
-// bit p = the k characters from p are all A/C/G/T (so p + k <= n - 1: the sentinel is not).  Words w + 1 .. w + ceil(k/64) + 1 are
-// read; the caller pads the bitmap with that many zero words.
-__global__ void k_valid_bits(const u64* acgt, u64 nw_data, u32 k, u64* valid) {
-  const u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= nw_data) return;
-  // first non-A/C/G/T position at or after 64 (w + 1), or far enough that no bit of this word cares
-  u64 nz = (w + 1) * 64 + k + 64;
-  const u32 look = (k + 63) / 64 + 1;
-  for (u32 j = 1; j <= look; ++j) {
-    const u64 z = ~acgt[w + j];
-    if (z) {
-      nz = (w + j) * 64 + (u64)__ffsll((long long)z) - 1;
-      break;
-    }
-  }
-  const u64 z0 = ~acgt[w];
-  u64 v = 0;
-  for (int b = 63; b >= 0; --b) {
-    const u64 p = w * 64 + (u64)b;
-    if ((z0 >> b) & 1ULL) nz = p;
-    v |= (u64)(nz - p >= k) << b;
-  }
-  valid[w] = v;
-}
-
-DG_DEV bool kmer_equal(const u8* t, u64 a, u64 b, u32 k) {
-  for (u32 j = 0; j < k; j += 8) {
-    u64 x = text8(t, a + j) ^ text8(t, b + j);
-    if (k - j < 8) x &= (1ULL << (8 * (k - j))) - 1;
-    if (x) return false;
-  }
-  return true;
-}
 
 // per rank i: bd bit i = a group of equal k-mers starts at rank i (every rank whose suffix has no valid k-mer is a group of its own),
 // hd bit i = that, and the k-mer at SA[i] is valid.  Launched with 256 threads per block: a wavefront's 64 ranks are one word.
@@ -205,14 +144,6 @@ __global__ void __launch_bounds__(256) k_heads(FmView f, u32 k, int forward_only
   wave_add(steps, n_ext);  // (every lane of the wavefront is here)
 }
 
-}  // namespace dg
-#include "map_mm.hpp"  // k_heads' sibling for e >= 1 mismatches
-#include "query_map.hpp"  // the same search per position of a query buffer (dg_query_map)
-#include "query_min_len.hpp"  // and the search for the smallest specific k per position (dg_query_min_len)
-#include "query_anchor.hpp"  // k_qmap with the k-mer's last bases matched exactly (dg_query_map_anchored)
-#include "query_min_len_end.hpp"  // the smallest specific k of the anchored k-mer that ENDS at a position (dg_query_min_len_end)
-namespace dg {
-
 // out[SA[i]] = the total of i's group (heads hold it in their own slot; members hold their head's rank), 0 for invalid ranks
 __global__ void k_scatter(FmView f, const u64* hd, const u32* start, u32 max_count, u32* out) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -252,6 +183,76 @@ static bool any_lane_busy(dg_index* ix) {  // as hunt.hip's
 static constexpr u64 MM_HEAD_CHUNK = 1ULL << 24;
 static constexpr u32 MM_NARROW = 8;
 
+// f(std::integral_constant<int, e>{}): the search kernels are templates on the mismatch count (e <= 2: every entry point checks)
+template <class F>
+static void with_mismatches(u32 e, F&& f) {
+  if (e == 0) f(std::integral_constant<int, 0>{});
+  else if (e == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 2>{});
+}
+
+// the transient device buffers of one call: released on its stream, in the order they were made, when the call returns
+struct Scratch {
+  hipStream_t st;
+  std::vector<std::pair<void*, bool>> made;  // (block, from big_alloc)
+  explicit Scratch(hipStream_t s) : st(s) {}
+  ~Scratch() {
+    (void)hipStreamSynchronize(st);
+    for (const auto& b : made) {
+      if (b.second) big_free(b.first, st);
+      else (void)hipFree(b.first);
+    }
+    (void)hipStreamSynchronize(st);
+  }
+  int big(void** p, size_t bytes) {
+    DG_HIP(big_alloc(p, bytes, st));
+    made.emplace_back(*p, true);
+    return DG_OK;
+  }
+  int small(void** p, size_t bytes) {
+    DG_HIP(hipMalloc(p, bytes));
+    made.emplace_back(*p, false);
+    return DG_OK;
+  }
+};
+
+// the events of a call with N phases, one of them a chunked search: N + 1 events around the phases and, with DICEY_TIMING, one in front of
+// every launch of the search, for the longest one.  Every event is owned from the moment it exists: a failed creation releases the others
+template <int N>
+struct ChunkTimer {
+  hipEvent_t ev[N + 1] = {};
+  std::vector<hipEvent_t> lev;
+  const bool timing = std::getenv("DICEY_TIMING") != nullptr;
+  ~ChunkTimer() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : lev) (void)hipEventDestroy(e);
+  }
+  int init() {
+    for (auto& e : ev) DG_HIP(hipEventCreate(&e));
+    return DG_OK;
+  }
+  int launch(hipStream_t st) {  // in front of every launch of the search
+    if (!timing) return DG_OK;
+    hipEvent_t e;
+    DG_HIP(hipEventCreate(&e));
+    lev.push_back(e);
+    DG_HIP(hipEventRecord(e, st));
+    return DG_OK;
+  }
+  // once the stream has been synchronised.  search: the phase the launches lie in (the last one ends where that phase does)
+  int read(float ms[N], int search, float* longest) {
+    for (int j = 0; j < N; ++j) DG_HIP(hipEventElapsedTime(&ms[j], ev[j], ev[j + 1]));
+    *longest = 0;
+    for (size_t j = 0; j < lev.size(); ++j) {
+      float t = 0;
+      DG_HIP(hipEventElapsedTime(&t, lev[j], j + 1 < lev.size() ? lev[j + 1] : ev[search + 1]));
+      *longest = std::max(*longest, t);
+    }
+    return DG_OK;
+  }
+};
+
 static int map_impl(dg_index* ix, const dg_map_params* prm, u32 mismatches, dg_map* m) {
   const FmView& f = ix->view;
   const u64 n = f.n;
@@ -273,93 +274,63 @@ static int map_impl(dg_index* ix, const dg_map_params* prm, u32 mismatches, dg_m
   if ((u64)free_b < need + (64ULL << 20))
     return fail(DG_ENOMEM, "dg_mappability: needs %llu MB of device memory, %llu MB free", (unsigned long long)(need >> 20),
                 (unsigned long long)(free_b >> 20));
-  struct Bufs {
-    hipStream_t st;
-    void *start = nullptr, *bm = nullptr, *scan = nullptr, *steps = nullptr;
-    ~Bufs() {
-      (void)hipStreamSynchronize(st);
-      if (start) big_free(start, st);
-      if (bm) big_free(bm, st);
-      if (scan) (void)hipFree(scan);
-      if (steps) (void)hipFree(steps);
-      (void)hipStreamSynchronize(st);
-    }
-  } b{st};
+  Scratch b(st);
+  void *b_start = nullptr, *b_bm = nullptr, *b_scan = nullptr, *b_steps = nullptr;
   DG_HIP(big_alloc((void**)&m->out, n * 4 + 256, st));
-  DG_HIP(big_alloc(&b.start, n * 4 + 256, st));
-  DG_HIP(big_alloc(&b.bm, 3 * bm_bytes, st));
-  DG_HIP(hipMalloc(&b.scan, scan_bytes));
-  DG_HIP(hipMalloc(&b.steps, sizeof(MmCounters)));
-  u64* acgt = (u64*)b.bm;  // becomes the boundary bitmap once the valid bitmap is made
+  DG_TRY(b.big(&b_start, n * 4 + 256));
+  DG_TRY(b.big(&b_bm, 3 * bm_bytes));
+  DG_TRY(b.small(&b_scan, scan_bytes));
+  DG_TRY(b.small(&b_steps, sizeof(MmCounters)));
+  u64* acgt = (u64*)b_bm;  // becomes the boundary bitmap once the valid bitmap is made
   u64* valid = acgt + nw;
   u64* hd = valid + nw;
   u64* bd = acgt;
-  u32* start = (u32*)b.start;
+  u32* start = (u32*)b_start;
   u32* end_rev = m->out;
-  hipEvent_t ev[5];
-  for (auto& e : ev) DG_HIP(hipEventCreate(&e));
-  struct Evs {
-    hipEvent_t* e;
-    ~Evs() {
-      for (int j = 0; j < 5; ++j) (void)hipEventDestroy(e[j]);
-    }
-  } evs{ev};
+  ChunkTimer<4> tm;  // valid | forward | reverse (the chunked search when e >= 1) | scatter
+  DG_TRY(tm.init());
   const u32 TB = 256;
-  DG_HIP(hipMemsetAsync(b.steps, 0, sizeof(MmCounters), st));
-  DG_HIP(hipEventRecord(ev[0], st));
+  DG_HIP(hipMemsetAsync(b_steps, 0, sizeof(MmCounters), st));
+  DG_HIP(hipEventRecord(tm.ev[0], st));
   hipLaunchKernelGGL(k_acgt_bits, dim3(ceil_div(nw, TB)), dim3(TB), 0, st, f.text, n, acgt, nw);
   DG_HIP(hipMemsetAsync(valid + nw_data, 0, (nw - nw_data) * 8, st));
   hipLaunchKernelGGL(k_valid_bits, dim3(ceil_div(nw_data, TB)), dim3(TB), 0, st, (const u64*)acgt, nw_data, k, valid);
-  DG_HIP(hipEventRecord(ev[1], st));
+  DG_HIP(hipEventRecord(tm.ev[1], st));
   hipLaunchKernelGGL(k_fwd_boundaries, dim3(ceil_div(n, TB)), dim3(TB), 0, st, f, (const u64*)valid, k, bd, hd);
-  DG_HIP(rocprim::inclusive_scan(b.scan, scan1, rocprim::make_transform_iterator(cnt0, StartKey{bd}), start, (size_t)n, MaxU32(), st));
-  DG_HIP(rocprim::inclusive_scan(b.scan, scan2, rocprim::make_transform_iterator(cnt0, EndKey{bd, n}), end_rev, (size_t)n, MinU32(), st));
-  DG_HIP(hipEventRecord(ev[2], st));
+  DG_HIP(rocprim::inclusive_scan(b_scan, scan1, rocprim::make_transform_iterator(cnt0, StartKey{bd}), start, (size_t)n, MaxU32(), st));
+  DG_HIP(rocprim::inclusive_scan(b_scan, scan2, rocprim::make_transform_iterator(cnt0, EndKey{bd, n}), end_rev, (size_t)n, MinU32(), st));
+  DG_HIP(hipEventRecord(tm.ev[2], st));
   u64 launches = 0;
-  std::vector<hipEvent_t> lev;  // DICEY_TIMING: one event per launch, for the longest one
-  struct LaunchEvs {
-    std::vector<hipEvent_t>& v;
-    ~LaunchEvs() {
-      for (hipEvent_t e : v) (void)hipEventDestroy(e);
-    }
-  } levs{lev};
   if (mismatches == 0) {
     hipLaunchKernelGGL(k_heads, dim3(ceil_div(n, TB)), dim3(TB), 0, st, f, k, prm->forward_only, (const u64*)hd, start, (const u32*)end_rev,
-                       (unsigned long long*)b.steps);
+                       (unsigned long long*)b_steps);
   } else {
     // head ranks in chunks, one launch each: no single launch holds the device for long
     u64 chunk = MM_HEAD_CHUNK;
     u32 W = MM_NARROW;
     if (const char* e = exp_env("DICEY_MAP_HEAD_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
     if (const char* e = exp_env("DICEY_MAP_NARROW")) W = (u32)std::min<u64>(std::strtoull(e, nullptr, 10), 0xFFFFFFFFull);
-    const bool timing = std::getenv("DICEY_TIMING") != nullptr;
-    MmCounters* ctr = (MmCounters*)b.steps;
+    MmCounters* ctr = (MmCounters*)b_steps;
     for (u64 r0 = 0; r0 < n; r0 += chunk, ++launches) {
       const u64 r1 = std::min(n, r0 + chunk);
-      if (timing) {
-        hipEvent_t e;
-        DG_HIP(hipEventCreate(&e));
-        lev.push_back(e);
-        DG_HIP(hipEventRecord(e, st));
-      }
-      if (mismatches == 1)
-        hipLaunchKernelGGL(k_heads_mm<1>, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, k, prm->forward_only, W, prm->max_count, r0, r1, (const u64*)hd,
-                           start, ctr);
-      else
-        hipLaunchKernelGGL(k_heads_mm<2>, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, k, prm->forward_only, W, prm->max_count, r0, r1, (const u64*)hd,
-                           start, ctr);
+      DG_TRY(tm.launch(st));
+      with_mismatches(mismatches, [&](auto E) {
+        if constexpr (E.value > 0)  // (e = 0 is k_heads above)
+          hipLaunchKernelGGL(k_heads_mm<E.value>, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, k, prm->forward_only, W, prm->max_count, r0, r1,
+                             (const u64*)hd, start, ctr);
+      });
     }
   }
-  DG_HIP(hipEventRecord(ev[3], st));
+  DG_HIP(hipEventRecord(tm.ev[3], st));
   hipLaunchKernelGGL(k_scatter, dim3(ceil_div(n, TB)), dim3(TB), 0, st, f, (const u64*)hd, (const u32*)start, prm->max_count, m->out);
-  DG_HIP(hipEventRecord(ev[4], st));
+  DG_HIP(hipEventRecord(tm.ev[4], st));
   MmCounters hc{};
-  if (mismatches == 0) DG_HIP(hipMemcpyAsync(&m->st.rev_steps, b.steps, 8, hipMemcpyDeviceToHost, st));
-  else DG_HIP(hipMemcpyAsync(&hc, b.steps, sizeof hc, hipMemcpyDeviceToHost, st));
+  if (mismatches == 0) DG_HIP(hipMemcpyAsync(&m->st.rev_steps, b_steps, 8, hipMemcpyDeviceToHost, st));
+  else DG_HIP(hipMemcpyAsync(&hc, b_steps, sizeof hc, hipMemcpyDeviceToHost, st));
   DG_HIP(hipStreamSynchronize(st));
   DG_HIP(hipGetLastError());
-  float ms[4] = {0, 0, 0, 0};
-  for (int j = 0; j < 4; ++j) DG_HIP(hipEventElapsedTime(&ms[j], ev[j], ev[j + 1]));
+  float ms[4] = {0, 0, 0, 0}, longest = 0;
+  DG_TRY(tm.read(ms, 2, &longest));
   m->st.ms_valid = ms[0];
   m->st.ms_forward = ms[1];
   m->st.ms_reverse = ms[2];
@@ -375,23 +346,12 @@ static int map_impl(dg_index* ix, const dg_map_params* prm, u32 mismatches, dg_m
     m->mm.early_exits = hc.early_exits;
     m->mm.launches = launches;
     m->mm.ms_search = ms[2];
-    if (!lev.empty()) {
-      float longest = 0;
-      for (size_t j = 0; j < lev.size(); ++j) {
-        float t = 0;
-        DG_HIP(hipEventElapsedTime(&t, lev[j], j + 1 < lev.size() ? lev[j + 1] : ev[3]));
-        longest = std::max(longest, t);
-      }
+    if (tm.timing && launches)
       std::fprintf(stderr, "dicey timing: mappability e=%u: %llu launches of the head search, %.1f ms in all, longest %.1f ms\n", mismatches,
                    (unsigned long long)launches, ms[2], longest);
-    }
   }
   return DG_OK;
 }
-
-}  // namespace dg
-#include "min_unique.hpp"  // the kernels of dg_min_unique
-namespace dg {
 
 // default ranks per launch of the two passes (the same reasoning as MM_HEAD_CHUNK: no launch holds a shared device for long)
 static constexpr u64 MU_CHUNK = 1ULL << 24;
@@ -409,80 +369,45 @@ static int min_unique_impl(dg_index* ix, u32 max_k, int forward_only, dg_map* m)
   if ((u64)free_b < need + (64ULL << 20))
     return fail(DG_ENOMEM, "dg_min_unique: needs %llu MB of device memory, %llu MB free", (unsigned long long)(need >> 20),
                 (unsigned long long)(free_b >> 20));
-  struct Bufs {
-    hipStream_t st;
-    void *lcp = nullptr, *steps = nullptr;
-    ~Bufs() {
-      (void)hipStreamSynchronize(st);
-      if (lcp) big_free(lcp, st);
-      if (steps) (void)hipFree(steps);
-      (void)hipStreamSynchronize(st);
-    }
-  } b{st};
+  Scratch b(st);
+  void *b_lcp = nullptr, *b_steps = nullptr;
   DG_HIP(big_alloc((void**)&m->out, n * 4 + 256, st));
-  DG_HIP(big_alloc(&b.lcp, lcp_bytes, st));
-  DG_HIP(hipMalloc(&b.steps, 8));
+  DG_TRY(b.big(&b_lcp, lcp_bytes));
+  DG_TRY(b.small(&b_steps, 8));
   u64 chunk = MU_CHUNK;
   if (const char* e = exp_env("DICEY_MAP_HEAD_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
-  const bool timing = std::getenv("DICEY_TIMING") != nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  struct Evs {  // in place before the first event exists: a failed creation releases the earlier ones
-    hipEvent_t* e;
-    ~Evs() {
-      for (int j = 0; j < 3; ++j)
-        if (e[j]) (void)hipEventDestroy(e[j]);
-    }
-  } evs{ev};
-  for (auto& e : ev) DG_HIP(hipEventCreate(&e));
-  std::vector<hipEvent_t> lev;  // DICEY_TIMING: one event per launch of the walk, for the longest one
-  struct LaunchEvs {
-    std::vector<hipEvent_t>& v;
-    ~LaunchEvs() {
-      for (hipEvent_t e : v) (void)hipEventDestroy(e);
-    }
-  } levs{lev};
+  ChunkTimer<2> tm;  // forward (k_mu_lcp) | reverse (the chunked walk)
+  DG_TRY(tm.init());
   const u32 TB = 256;
-  DG_HIP(hipMemsetAsync(b.steps, 0, 8, st));
-  DG_HIP(hipEventRecord(ev[0], st));
+  DG_HIP(hipMemsetAsync(b_steps, 0, 8, st));
+  DG_HIP(hipEventRecord(tm.ev[0], st));
   for (u64 r0 = 0; r0 < n + 1; r0 += chunk) {  // ranks 0..n: lcp[n] closes the array
     const u64 r1 = std::min(n + 1, r0 + chunk);
-    hipLaunchKernelGGL(k_mu_lcp, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, max_k, r0, r1, (u16*)b.lcp);
+    hipLaunchKernelGGL(k_mu_lcp, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, max_k, r0, r1, (u16*)b_lcp);
   }
-  DG_HIP(hipEventRecord(ev[1], st));
+  DG_HIP(hipEventRecord(tm.ev[1], st));
   u64 launches = 0;
   for (u64 r0 = 0; r0 < n; r0 += chunk, ++launches) {
     const u64 r1 = std::min(n, r0 + chunk);
-    if (timing) {
-      hipEvent_t e;
-      DG_HIP(hipEventCreate(&e));
-      lev.push_back(e);
-      DG_HIP(hipEventRecord(e, st));
-    }
-    hipLaunchKernelGGL(k_mu_walk, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, max_k, forward_only, r0, r1, (const u16*)b.lcp, m->out,
-                       (unsigned long long*)b.steps);
+    DG_TRY(tm.launch(st));
+    hipLaunchKernelGGL(k_mu_walk, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, max_k, forward_only, r0, r1, (const u16*)b_lcp, m->out,
+                       (unsigned long long*)b_steps);
   }
-  DG_HIP(hipEventRecord(ev[2], st));
-  DG_HIP(hipMemcpyAsync(&m->st.rev_steps, b.steps, 8, hipMemcpyDeviceToHost, st));
+  DG_HIP(hipEventRecord(tm.ev[2], st));
+  DG_HIP(hipMemcpyAsync(&m->st.rev_steps, b_steps, 8, hipMemcpyDeviceToHost, st));
   DG_HIP(hipStreamSynchronize(st));
   DG_HIP(hipGetLastError());
-  float ms[2] = {0, 0};
-  for (int j = 0; j < 2; ++j) DG_HIP(hipEventElapsedTime(&ms[j], ev[j], ev[j + 1]));
+  float ms[2] = {0, 0}, longest = 0;
+  DG_TRY(tm.read(ms, 1, &longest));
   m->st.ms_valid = 0;
   m->st.ms_forward = ms[0];
   m->st.ms_reverse = ms[1];
   m->st.ms_scatter = 0;  // the walk writes the value itself
   m->st.ms_total = (double)ms[0] + (double)ms[1];  // in double: exactly the sum of the reported parts
   m->st.transient_bytes = lcp_bytes;
-  if (!lev.empty()) {
-    float longest = 0;
-    for (size_t j = 0; j < lev.size(); ++j) {
-      float t = 0;
-      DG_HIP(hipEventElapsedTime(&t, lev[j], j + 1 < lev.size() ? lev[j + 1] : ev[2]));
-      longest = std::max(longest, t);
-    }
+  if (tm.timing && launches)
     std::fprintf(stderr, "dicey timing: min unique max_k=%u: %llu launches of the walk, %.1f ms in all, longest %.1f ms\n", max_k,
                  (unsigned long long)launches, ms[1], longest);
-  }
   return DG_OK;
 }
 
@@ -532,21 +457,13 @@ static int query_args_check(const char* who, dg_index* ix, const uint8_t* seqs, 
 }
 
 // The device side of a query buffer: the bytes in whole 64-byte blocks with the text's slack behind, one u32 per position, `nbm` bitmaps
-// of nw words each (the A/C/G/T bitmap first) and a counter record.  alloc() checks the free memory and allocates everything; upload()
-// queues the copy and k_acgt_bits.
+// of nw words each (the A/C/G/T bitmap first, the valid bitmap second) and a counter record.  alloc() checks the free memory and allocates
+// everything; upload() queues the copy and k_acgt_bits.
 struct QueryDev {
-  hipStream_t st;
+  Scratch mem;
   u64 qn = 0, nw_data = 0, nw = 0, q_bytes = 0;
   void *q = nullptr, *out = nullptr, *bm = nullptr, *ctr = nullptr;
-  explicit QueryDev(hipStream_t s) : st(s) {}
-  ~QueryDev() {
-    (void)hipStreamSynchronize(st);
-    if (q) big_free(q, st);
-    if (out) big_free(out, st);
-    if (bm) big_free(bm, st);
-    if (ctr) (void)hipFree(ctr);
-    (void)hipStreamSynchronize(st);
-  }
+  explicit QueryDev(hipStream_t s) : mem(s) {}
   // k: the longest k-mer looked at, which sizes the zero words behind the bitmap's data
   int alloc(const char* who, u64 qn_, u32 k, u32 nbm, size_t ctr_bytes) {
     qn = qn_;
@@ -560,14 +477,16 @@ struct QueryDev {
     if ((u64)free_b < need + (64ULL << 20))
       return fail(DG_ENOMEM, "%s: needs %llu MB of device memory, %llu MB free", who, (unsigned long long)(need >> 20),
                   (unsigned long long)(free_b >> 20));
-    DG_HIP(big_alloc(&q, q_bytes, st));
-    DG_HIP(big_alloc(&out, qn * 4 + 256, st));
-    DG_HIP(big_alloc(&bm, nbm * bm_bytes, st));
-    DG_HIP(hipMalloc(&ctr, ctr_bytes));
+    DG_TRY(mem.big(&q, q_bytes));
+    DG_TRY(mem.big(&out, qn * 4 + 256));
+    DG_TRY(mem.big(&bm, nbm * bm_bytes));
+    DG_TRY(mem.small(&ctr, ctr_bytes));
     return DG_OK;
   }
   u64* acgt() const { return (u64*)bm; }
+  u64* valid() const { return acgt() + nw; }
   int upload(const std::vector<u8>& hq) {
+    hipStream_t st = mem.st;
     DG_HIP(hipMemsetAsync((u8*)q + (qn & ~63ULL), 0, q_bytes - (qn & ~63ULL), st));  // the tail of the last block and the slack
     DG_HIP(hipMemcpyAsync(q, hq.data(), qn, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_acgt_bits, dim3(ceil_div(nw, 256)), dim3(256), 0, st, (const u8*)q, qn, acgt(), nw);
@@ -575,113 +494,92 @@ struct QueryDev {
   }
 };
 
-// the events of a chunked search: upload | search, and with DICEY_TIMING one per launch, for the longest one
-struct ChunkTimer {
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  std::vector<hipEvent_t> lev;
-  const bool timing = std::getenv("DICEY_TIMING") != nullptr;
-  ~ChunkTimer() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : lev) (void)hipEventDestroy(e);
-  }
-  int init() {
-    for (auto& e : ev) DG_HIP(hipEventCreate(&e));
-    return DG_OK;
-  }
-  int launch(hipStream_t st) {  // in front of every launch of the search
-    if (!timing) return DG_OK;
-    hipEvent_t e;
-    DG_HIP(hipEventCreate(&e));
-    lev.push_back(e);
-    DG_HIP(hipEventRecord(e, st));
-    return DG_OK;
-  }
-  int read(float ms[2], float* longest) {  // once the stream has been synchronised
-    for (int j = 0; j < 2; ++j) DG_HIP(hipEventElapsedTime(&ms[j], ev[j], ev[j + 1]));
-    *longest = 0;
-    for (size_t j = 0; j < lev.size(); ++j) {
-      float t = 0;
-      DG_HIP(hipEventElapsedTime(&t, lev[j], j + 1 < lev.size() ? lev[j + 1] : ev[2]));
-      *longest = std::max(*longest, t);
-    }
-    return DG_OK;
-  }
+// what tells the two query searches apart on the host, beside their kernels and counters
+struct QueryKind {
+  u32 nbm;            // bitmaps: 2 when k_valid_bits runs (one k for all positions), 1 when a lane finds its own limit
+  u64 chunk;          // default positions per launch
+  const char* chunk_env;
 };
+static constexpr QueryKind QUERY_MAP = {2, QMAP_CHUNK, "DICEY_QMAP_CHUNK"}, QUERY_MIN_LEN = {1, QMINLEN_CHUNK, "DICEY_QMINLEN_CHUNK"};
 
-// hq: the records as REC1 '\n' REC2 '\n' ... (qn bytes); vals: u32[qn], one value per buffer position.  anchor: null for dg_query_map
-// (k_qmap), else the number of last bases matched exactly (k_qmap_anch): the same buffers, chunks and W either way
-static int query_map_impl(const char* who, dg_index* ix, const dg_qmap_params* prm, const u32* anchor, const std::vector<u8>& hq, std::vector<u32>& vals,
-                          dg_qmap_stats_t* stt) {
-  const FmView& f = ix->view;
+// The driver of every dg_query_* call.  hq: the records as REC1 '\n' REC2 '\n' ... (qn bytes); vals: u32[qn], one value per buffer
+// position; k: the longest k-mer looked at; label: what the DICEY_TIMING line calls the search.  launch(b, W, p0, p1, grid, block) queues the
+// kernel for positions [p0, p1).  Fills *hc with the device counters and the fields every stats struct has; the caller adds its own.
+template <class Counters, class Stats, class Launch>
+static int query_run(const char* who, dg_index* ix, const QueryKind& kind, u32 k, const char* label, const std::vector<u8>& hq, std::vector<u32>& vals,
+                     Counters* hc, Stats* stt, Launch launch) {
   const u64 qn = hq.size();
-  const u32 k = prm->k;
   hipStream_t st = ix->stream;
   QueryDev b(st);
-  DG_TRY(b.alloc(who, qn, k, 2, sizeof(QmapCounters)));
-  u64 chunk = QMAP_CHUNK;
+  DG_TRY(b.alloc(who, qn, k, kind.nbm, sizeof(Counters)));
+  u64 chunk = kind.chunk;
   u32 W = MM_NARROW;
-  if (const char* e = exp_env("DICEY_QMAP_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
+  if (const char* e = exp_env(kind.chunk_env)) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
   if (const char* e = exp_env("DICEY_MAP_NARROW")) W = (u32)std::min<u64>(std::strtoull(e, nullptr, 10), 0xFFFFFFFFull);
-  ChunkTimer tm;
+  ChunkTimer<2> tm;  // upload and bitmaps | the chunked search
   DG_TRY(tm.init());
-  const u8* q = (const u8*)b.q;
-  const u64 nw = b.nw, nw_data = b.nw_data;
-  u64* acgt = b.acgt();
-  u64* valid = acgt + nw;
-  QmapCounters* ctr = (QmapCounters*)b.ctr;
   const u32 TB = 256;
-  DG_HIP(hipMemsetAsync(b.ctr, 0, sizeof(QmapCounters), st));
+  DG_HIP(hipMemsetAsync(b.ctr, 0, sizeof(Counters), st));
   DG_HIP(hipEventRecord(tm.ev[0], st));
   DG_TRY(b.upload(hq));
-  DG_HIP(hipMemsetAsync(valid + nw_data, 0, (nw - nw_data) * 8, st));
-  hipLaunchKernelGGL(k_valid_bits, dim3(ceil_div(nw_data, TB)), dim3(TB), 0, st, (const u64*)acgt, nw_data, k, valid);
+  if (kind.nbm > 1) {
+    DG_HIP(hipMemsetAsync(b.valid() + b.nw_data, 0, (b.nw - b.nw_data) * 8, st));
+    hipLaunchKernelGGL(k_valid_bits, dim3(ceil_div(b.nw_data, TB)), dim3(TB), 0, st, (const u64*)b.acgt(), b.nw_data, k, b.valid());
+  }
   DG_HIP(hipEventRecord(tm.ev[1], st));
   u64 launches = 0;
   for (u64 p0 = 0; p0 < qn; p0 += chunk, ++launches) {  // positions in chunks, one launch each: no single launch holds the device for long
     const u64 p1 = std::min(qn, p0 + chunk);
     DG_TRY(tm.launch(st));
-    const dim3 grid(ceil_div(p1 - p0, TB));
-    if (anchor) {
-      if (prm->mismatches == 0)
-        hipLaunchKernelGGL(k_qmap_anch<0>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, *anchor, prm->forward_only, W, prm->max_count, p0, p1,
-                           (u32*)b.out, ctr);
-      else if (prm->mismatches == 1)
-        hipLaunchKernelGGL(k_qmap_anch<1>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, *anchor, prm->forward_only, W, prm->max_count, p0, p1,
-                           (u32*)b.out, ctr);
-      else
-        hipLaunchKernelGGL(k_qmap_anch<2>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, *anchor, prm->forward_only, W, prm->max_count, p0, p1,
-                           (u32*)b.out, ctr);
-    } else if (prm->mismatches == 0)
-      hipLaunchKernelGGL(k_qmap<0>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, prm->forward_only, W, prm->max_count, p0, p1, (u32*)b.out, ctr);
-    else if (prm->mismatches == 1)
-      hipLaunchKernelGGL(k_qmap<1>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, prm->forward_only, W, prm->max_count, p0, p1, (u32*)b.out, ctr);
-    else
-      hipLaunchKernelGGL(k_qmap<2>, grid, dim3(TB), 0, st, f, q, (const u64*)valid, k, prm->forward_only, W, prm->max_count, p0, p1, (u32*)b.out, ctr);
+    launch(b, W, p0, p1, dim3(ceil_div(p1 - p0, TB)), dim3(TB));
   }
   DG_HIP(hipEventRecord(tm.ev[2], st));
-  QmapCounters hc{};
-  DG_HIP(hipMemcpyAsync(&hc, b.ctr, sizeof hc, hipMemcpyDeviceToHost, st));
+  DG_HIP(hipMemcpyAsync(hc, b.ctr, sizeof *hc, hipMemcpyDeviceToHost, st));
   DG_HIP(hipMemcpyAsync(vals.data(), b.out, qn * 4, hipMemcpyDeviceToHost, st));
   DG_HIP(hipStreamSynchronize(st));
   DG_HIP(hipGetLastError());
   float ms[2] = {0, 0}, longest = 0;
-  DG_TRY(tm.read(ms, &longest));
-  stt->valid = hc.valid;
-  stt->steps = hc.steps;
-  stt->table_reads = hc.table_reads;
-  stt->verified_rows = hc.verified_rows;
-  stt->early_exits = hc.early_exits;
+  DG_TRY(tm.read(ms, 1, &longest));
+  stt->valid = hc->valid;
+  stt->steps = hc->steps;
+  stt->table_reads = hc->table_reads;
+  stt->verified_rows = hc->verified_rows;
   stt->launches = launches;
   stt->ms_valid = ms[0];
   stt->ms_search = ms[1];
   stt->ms_total = (double)ms[0] + (double)ms[1];  // in double: exactly the sum of the reported parts
-  if (tm.timing && launches && anchor)
-    std::fprintf(stderr, "dicey timing: query map e=%u anchor=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n", prm->mismatches,
-                 *anchor, (unsigned long long)launches, ms[1], longest);
-  else if (tm.timing && launches)
-    std::fprintf(stderr, "dicey timing: query map e=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n", prm->mismatches,
-                 (unsigned long long)launches, ms[1], longest);
+  if (tm.timing && launches)
+    std::fprintf(stderr, "dicey timing: %s: %llu launches of the search, %.1f ms in all, longest %.1f ms\n", label, (unsigned long long)launches,
+                 ms[1], longest);
+  return DG_OK;
+}
+
+// "query map e=1" or, with an anchor, "query map e=1 anchor=5"
+static std::string query_label(const char* what, u32 mismatches, const u32* anchor) {
+  char s[96];
+  if (anchor) std::snprintf(s, sizeof s, "%s e=%u anchor=%u", what, mismatches, *anchor);
+  else std::snprintf(s, sizeof s, "%s e=%u", what, mismatches);
+  return s;
+}
+
+// k_qmap per chunk of positions.  anchor: null for dg_query_map, else the number of last bases matched exactly (k_qmap_anch): the same
+// buffers, chunks and W either way
+static int query_map_impl(const char* who, dg_index* ix, const dg_qmap_params* prm, const u32* anchor, const std::vector<u8>& hq, std::vector<u32>& vals,
+                          dg_qmap_stats_t* stt) {
+  const FmView& f = ix->view;
+  QmapCounters hc{};
+  DG_TRY(query_run(who, ix, QUERY_MAP, prm->k, query_label("query map", prm->mismatches, anchor).c_str(), hq, vals, &hc, stt,
+                   [&](const QueryDev& b, u32 W, u64 p0, u64 p1, dim3 grid, dim3 block) {
+                     with_mismatches(prm->mismatches, [&](auto E) {
+                       if (anchor)
+                         hipLaunchKernelGGL(k_qmap_anch<E.value>, grid, block, 0, b.mem.st, f, (const u8*)b.q, (const u64*)b.valid(), prm->k, *anchor,
+                                            prm->forward_only, W, prm->max_count, p0, p1, (u32*)b.out, (QmapCounters*)b.ctr);
+                       else
+                         hipLaunchKernelGGL(k_qmap<E.value>, grid, block, 0, b.mem.st, f, (const u8*)b.q, (const u64*)b.valid(), prm->k, prm->forward_only, W,
+                                            prm->max_count, p0, p1, (u32*)b.out, (QmapCounters*)b.ctr);
+                     });
+                   }));
+  stt->early_exits = hc.early_exits;
   return DG_OK;
 }
 
@@ -690,77 +588,43 @@ static int query_map_impl(const char* who, dg_index* ix, const dg_qmap_params* p
 static int query_min_len_impl(const char* who, dg_index* ix, const dg_qminlen_params* prm, const u32* anchor, const std::vector<u8>& hq,
                               std::vector<u32>& vals, dg_qminlen_stats_t* stt) {
   const FmView& f = ix->view;
-  const u64 qn = hq.size();
-  hipStream_t st = ix->stream;
-  QueryDev b(st);
-  DG_TRY(b.alloc(who, qn, prm->max_k, 1, sizeof(QminlenCounters)));
-  u64 chunk = QMINLEN_CHUNK;
-  u32 W = MM_NARROW;
-  if (const char* e = exp_env("DICEY_QMINLEN_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
-  if (const char* e = exp_env("DICEY_MAP_NARROW")) W = (u32)std::min<u64>(std::strtoull(e, nullptr, 10), 0xFFFFFFFFull);
-  ChunkTimer tm;
-  DG_TRY(tm.init());
-  const u8* q = (const u8*)b.q;
-  const u64* acgt = b.acgt();
-  QminlenCounters* ctr = (QminlenCounters*)b.ctr;
-  const u32 TB = 256;
-  DG_HIP(hipMemsetAsync(b.ctr, 0, sizeof(QminlenCounters), st));
-  DG_HIP(hipEventRecord(tm.ev[0], st));
-  DG_TRY(b.upload(hq));
-  DG_HIP(hipEventRecord(tm.ev[1], st));
-  u64 launches = 0;
-  for (u64 p0 = 0; p0 < qn; p0 += chunk, ++launches) {  // positions in chunks, one launch each: no single launch holds the device for long
-    const u64 p1 = std::min(qn, p0 + chunk);
-    DG_TRY(tm.launch(st));
-    const dim3 grid(ceil_div(p1 - p0, TB));
-    if (anchor) {
-      if (prm->mismatches == 0)
-        hipLaunchKernelGGL(k_qminlen_end<0>, grid, dim3(TB), 0, st, f, q, acgt, prm->min_k, prm->max_k, *anchor, prm->forward_only, W, prm->at_most, p0,
-                           p1, (u32*)b.out, ctr);
-      else if (prm->mismatches == 1)
-        hipLaunchKernelGGL(k_qminlen_end<1>, grid, dim3(TB), 0, st, f, q, acgt, prm->min_k, prm->max_k, *anchor, prm->forward_only, W, prm->at_most, p0,
-                           p1, (u32*)b.out, ctr);
-      else
-        hipLaunchKernelGGL(k_qminlen_end<2>, grid, dim3(TB), 0, st, f, q, acgt, prm->min_k, prm->max_k, *anchor, prm->forward_only, W, prm->at_most, p0,
-                           p1, (u32*)b.out, ctr);
-    } else if (prm->mismatches == 0)
-      hipLaunchKernelGGL(k_qminlen<0>, grid, dim3(TB), 0, st, f, q, acgt, b.nw, prm->min_k, prm->max_k, prm->forward_only, W, prm->at_most, p0, p1,
-                         (u32*)b.out, ctr);
-    else if (prm->mismatches == 1)
-      hipLaunchKernelGGL(k_qminlen<1>, grid, dim3(TB), 0, st, f, q, acgt, b.nw, prm->min_k, prm->max_k, prm->forward_only, W, prm->at_most, p0, p1,
-                         (u32*)b.out, ctr);
-    else
-      hipLaunchKernelGGL(k_qminlen<2>, grid, dim3(TB), 0, st, f, q, acgt, b.nw, prm->min_k, prm->max_k, prm->forward_only, W, prm->at_most, p0, p1,
-                         (u32*)b.out, ctr);
-  }
-  DG_HIP(hipEventRecord(tm.ev[2], st));
   QminlenCounters hc{};
-  DG_HIP(hipMemcpyAsync(&hc, b.ctr, sizeof hc, hipMemcpyDeviceToHost, st));
-  DG_HIP(hipMemcpyAsync(vals.data(), b.out, qn * 4, hipMemcpyDeviceToHost, st));
-  DG_HIP(hipStreamSynchronize(st));
-  DG_HIP(hipGetLastError());
-  float ms[2] = {0, 0}, longest = 0;
-  DG_TRY(tm.read(ms, &longest));
+  DG_TRY(query_run(who, ix, QUERY_MIN_LEN, prm->max_k, query_label(anchor ? "query min length by end" : "query min length", prm->mismatches, anchor).c_str(),
+                   hq, vals, &hc, stt, [&](const QueryDev& b, u32 W, u64 p0, u64 p1, dim3 grid, dim3 block) {
+                     with_mismatches(prm->mismatches, [&](auto E) {
+                       if (anchor)
+                         hipLaunchKernelGGL(k_qminlen_end<E.value>, grid, block, 0, b.mem.st, f, (const u8*)b.q, (const u64*)b.acgt(), prm->min_k, prm->max_k,
+                                            *anchor, prm->forward_only, W, prm->at_most, p0, p1, (u32*)b.out, (QminlenCounters*)b.ctr);
+                       else
+                         hipLaunchKernelGGL(k_qminlen<E.value>, grid, block, 0, b.mem.st, f, (const u8*)b.q, (const u64*)b.acgt(), b.nw, prm->min_k, prm->max_k,
+                                            prm->forward_only, W, prm->at_most, p0, p1, (u32*)b.out, (QminlenCounters*)b.ctr);
+                     });
+                   }));
   u64 found = 0;
   for (u32 v : vals) found += v != 0 && v != QMAP_INVALID;
-  stt->valid = hc.valid;
   stt->found = found;
   stt->probes = hc.probes;
-  stt->steps = hc.steps;
-  stt->table_reads = hc.table_reads;
-  stt->verified_rows = hc.verified_rows;
-  stt->launches = launches;
-  stt->ms_valid = ms[0];
-  stt->ms_search = ms[1];
-  stt->ms_total = (double)ms[0] + (double)ms[1];  // in double: exactly the sum of the reported parts
-  if (tm.timing && launches && anchor)
-    std::fprintf(stderr, "dicey timing: query min length by end e=%u anchor=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n",
-                 prm->mismatches, *anchor, (unsigned long long)launches, ms[1], longest);
-  else if (tm.timing && launches)
-    std::fprintf(stderr, "dicey timing: query min length e=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n", prm->mismatches,
-                 (unsigned long long)launches, ms[1], longest);
   return DG_OK;
 }
+
+// What the four dg_query_* entry points do once their parameter block is checked: totals, device, pack, search, unpack, stats.
+// search(hq, vals, &st) is query_map_impl or query_min_len_impl with the caller's name and parameters
+template <class Stats, class Search>
+static int query_call(dg_index* ix, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values, Stats* stats, Search search) {
+  const u64 total = (off && nseq) ? off[nseq] : 0;
+  Stats st{};
+  st.positions = nseq ? total - off[0] : 0;
+  if (total) {
+    DG_HIP(hipSetDevice(ix->device));
+    const std::vector<u8> hq = query_pack(seqs, off, nseq);
+    std::vector<u32> vals(hq.size());
+    DG_TRY(search(hq, vals, &st));
+    query_unpack(vals, off, nseq, values);
+  }
+  if (stats) *stats = st;
+  return DG_OK;
+}
+
 
 }  // namespace dg
 
@@ -827,18 +691,9 @@ int dg_query_map(dg_index* ix, const dg_qmap_params* p, const uint8_t* seqs, con
   if (p->k < 10 || p->k > 1000) return fail(DG_ELIMIT, "dg_query_map: k = %u outside 10..1000", p->k);
   if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_query_map: %u mismatches outside 0..2", p->mismatches);
   DG_TRY(query_args_check("dg_query_map", ix, seqs, off, nseq, values, false));
-  const u64 total = (off && nseq) ? off[nseq] : 0;
-  dg_qmap_stats_t st{};
-  st.positions = nseq ? total - off[0] : 0;
-  if (total) {
-    DG_HIP(hipSetDevice(ix->device));
-    const std::vector<u8> hq = query_pack(seqs, off, nseq);
-    std::vector<u32> vals(hq.size());
-    DG_TRY(query_map_impl("dg_query_map", ix, p, nullptr, hq, vals, &st));
-    query_unpack(vals, off, nseq, values);
-  }
-  if (stats) *stats = st;
-  return DG_OK;
+  return query_call(ix, seqs, off, nseq, values, stats, [&](const std::vector<u8>& hq, std::vector<u32>& vals, dg_qmap_stats_t* st) {
+    return query_map_impl("dg_query_map", ix, p, nullptr, hq, vals, st);
+  });
 }
 
 int dg_query_map_anchored(dg_index* ix, const dg_qmap_anchor_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
@@ -849,19 +704,10 @@ int dg_query_map_anchored(dg_index* ix, const dg_qmap_anchor_params* p, const ui
   if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_query_map_anchored: %u mismatches outside 0..2", p->mismatches);
   if (p->anchor > p->k) return fail(DG_ELIMIT, "dg_query_map_anchored: anchor = %u above k = %u", p->anchor, p->k);
   DG_TRY(query_args_check("dg_query_map_anchored", ix, seqs, off, nseq, values, true));
-  const u64 total = (off && nseq) ? off[nseq] : 0;
-  dg_qmap_stats_t st{};
-  st.positions = nseq ? total - off[0] : 0;
-  if (total) {
-    DG_HIP(hipSetDevice(ix->device));
-    const dg_qmap_params q = {p->k, p->mismatches, p->forward_only, p->max_count, 0u, {0u, 0u, 0u}};
-    const std::vector<u8> hq = query_pack(seqs, off, nseq);
-    std::vector<u32> vals(hq.size());
-    DG_TRY(query_map_impl("dg_query_map_anchored", ix, &q, &p->anchor, hq, vals, &st));
-    query_unpack(vals, off, nseq, values);
-  }
-  if (stats) *stats = st;
-  return DG_OK;
+  const dg_qmap_params q = {p->k, p->mismatches, p->forward_only, p->max_count, 0u, {0u, 0u, 0u}};
+  return query_call(ix, seqs, off, nseq, values, stats, [&](const std::vector<u8>& hq, std::vector<u32>& vals, dg_qmap_stats_t* st) {
+    return query_map_impl("dg_query_map_anchored", ix, &q, &p->anchor, hq, vals, st);
+  });
 }
 
 int dg_query_min_len(dg_index* ix, const dg_qminlen_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
@@ -874,18 +720,9 @@ int dg_query_min_len(dg_index* ix, const dg_qminlen_params* p, const uint8_t* se
   if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_query_min_len: %u mismatches outside 0..2", p->mismatches);
   if (p->at_most > 0xFFFFFFFDu) return fail(DG_ELIMIT, "dg_query_min_len: at_most = %u above 4294967293", p->at_most);
   DG_TRY(query_args_check("dg_query_min_len", ix, seqs, off, nseq, values, true));
-  const u64 total = (off && nseq) ? off[nseq] : 0;
-  dg_qminlen_stats_t st{};
-  st.positions = nseq ? total - off[0] : 0;
-  if (total) {
-    DG_HIP(hipSetDevice(ix->device));
-    const std::vector<u8> hq = query_pack(seqs, off, nseq);
-    std::vector<u32> vals(hq.size());
-    DG_TRY(query_min_len_impl("dg_query_min_len", ix, p, nullptr, hq, vals, &st));
-    query_unpack(vals, off, nseq, values);
-  }
-  if (stats) *stats = st;
-  return DG_OK;
+  return query_call(ix, seqs, off, nseq, values, stats, [&](const std::vector<u8>& hq, std::vector<u32>& vals, dg_qminlen_stats_t* st) {
+    return query_min_len_impl("dg_query_min_len", ix, p, nullptr, hq, vals, st);
+  });
 }
 
 int dg_query_min_len_end(dg_index* ix, const dg_qminlen_end_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
@@ -899,20 +736,12 @@ int dg_query_min_len_end(dg_index* ix, const dg_qminlen_end_params* p, const uin
   if (p->at_most > 0xFFFFFFFDu) return fail(DG_ELIMIT, "dg_query_min_len_end: at_most = %u above 4294967293", p->at_most);
   if (p->anchor > p->min_k) return fail(DG_ELIMIT, "dg_query_min_len_end: anchor = %u above min_k = %u", p->anchor, p->min_k);
   DG_TRY(query_args_check("dg_query_min_len_end", ix, seqs, off, nseq, values, true));
-  const u64 total = (off && nseq) ? off[nseq] : 0;
-  dg_qminlen_stats_t st{};
-  st.positions = nseq ? total - off[0] : 0;
-  if (total) {
-    DG_HIP(hipSetDevice(ix->device));
-    const dg_qminlen_params q = {p->min_k, p->max_k, p->mismatches, p->forward_only, p->at_most, 0u, {0u, 0u}};
-    const std::vector<u8> hq = query_pack(seqs, off, nseq);
-    std::vector<u32> vals(hq.size());
-    DG_TRY(query_min_len_impl("dg_query_min_len_end", ix, &q, &p->anchor, hq, vals, &st));
-    query_unpack(vals, off, nseq, values);
-  }
-  if (stats) *stats = st;
-  return DG_OK;
+  const dg_qminlen_params q = {p->min_k, p->max_k, p->mismatches, p->forward_only, p->at_most, 0u, {0u, 0u}};
+  return query_call(ix, seqs, off, nseq, values, stats, [&](const std::vector<u8>& hq, std::vector<u32>& vals, dg_qminlen_stats_t* st) {
+    return query_min_len_impl("dg_query_min_len_end", ix, &q, &p->anchor, hq, vals, st);
+  });
 }
+
 
 int dg_map_mm_stats(const dg_map* m, dg_map_mm_stats_t* out) {
   if (!m || !out) return fail(DG_EINVAL, "dg_map_mm_stats: null argument");

@@ -24,9 +24,9 @@
 //            (answer 0: still on the other strand at limit(p)).  The value goes to out[SA[i]] from the same kernel.
 // The walk is the one k_heads takes at k = max_k (left at the first empty interval), per rank instead of per group head and only
 // where F <= limit(p): no narrow-interval finish on the text is built on top of it (DESIGN.md §10 has the reasoning and the figures).
-// Included by mappability.hip behind text8 / acgt_code and map_mm.hpp's mm_acgt_bytes.
 #pragma once
-#include "devfm.hpp"
+#include "map_mm.hpp"  // mm_acgt_bytes
+#include "text_bits.hpp"
 
 namespace dg {
 

@@ -17,7 +17,6 @@
 // strand from p + k - m (m <= k: never in front of p, so never in front of the buffer for the first record at offset 0, the smallest probe
 // k = min_k and a record of exactly min_k bytes included) to below p + k + 8.  p + k <= qn - 1 (the record's '\n'), and the buffer has the
 // rest of its 64-byte block and 64 bytes of slack behind qn: the bounds are k_qmap's.
-// Included by mappability.hip behind query_map.hpp.
 #pragma once
 #include "query_map.hpp"
 
@@ -34,14 +33,7 @@ __global__ void __launch_bounds__(256) k_qminlen(FmView f, const u8* q, const u6
                                                 u64 p0, u64 p1, u32* out, QminlenCounters* ctr) {
   const u64 i = p0 + (u64)blockIdx.x * blockDim.x + threadIdx.x;
   MmLane c;
-  c.pat = q;
-  c.p = i;
-  c.k = min_k;
-  c.rev = false;
-  c.W = W;
-  c.cap = t + 1;
-  c.total = 0;
-  c.steps = c.tab = c.rows = 0;
+  mm_lane_init(c, q, i, min_k, W, t + 1);
   u32 ok = 0, probes = 0;
   if (i < p1) {
     // limit(p): the first byte that is not A/C/G/T at or behind p, no further than max_k away
@@ -74,7 +66,7 @@ __global__ void __launch_bounds__(256) k_qminlen(FmView f, const u8* q, const u6
         c.total = 0;
 #pragma nounroll
         for (u32 s = 0; s < strands && c.total < c.cap; ++s) {
-          c.rev = s != 0;
+          mm_set_strand(c, s != 0);
           mm_strand<E>(f, c);
         }
         ++probes;
@@ -99,9 +91,7 @@ __global__ void __launch_bounds__(256) k_qminlen(FmView f, const u8* q, const u6
   }
   wave_add(&ctr->valid, ok);  // (every lane of the wavefront is here)
   wave_add(&ctr->probes, probes);
-  wave_add(&ctr->steps, c.steps);
-  wave_add(&ctr->table_reads, c.tab);
-  wave_add(&ctr->verified_rows, c.rows);
+  mm_flush(ctr, c);
 }
 
 }  // namespace dg

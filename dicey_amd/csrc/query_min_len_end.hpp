@@ -3,7 +3,7 @@
 // mismatches and with its last a bases exact, both strands: the 3' end stays where it is and the oligo grows at its 5' end.
 //
 // The buffer, the lane layout and the probe order are k_qminlen's (query_min_len.hpp); the search of one probe is k_qmap_anch's
-// (query_anchor.hpp: anch_strand<E> on an AnchLane, unchanged).  What is new is the direction:
+// (query_anchor.hpp: mm_strand<E> on an AnchLane, unchanged).  What is new is the direction:
 //   limit    brun(p), the A/C/G/T bytes that end at p, read off the bitmap of k_acgt_bits towards word 0 and cut at max_k: the nearest clear
 //            bit at or in front of p (the word shifted left by 63 - (p & 63), __clzll), at most max_k/64 + 2 words, none in front of word 0
 //            (the first record starts at buffer offset 0 with no '\n' in front of it: word 0 exhausted means the run starts at 0).
@@ -20,7 +20,6 @@
 // [start + j, start + j + 8) with j < k on the forward strand, so they end below p + 1 + 15 <= qn + 14 (p <= qn - 2: the last byte is a
 // '\n'), inside the rest of the 64-byte block and the 64 bytes of slack behind qn; on the other strand it reads from start + k - m
 // (m <= k: never in front of the start, so never in front of the buffer for the first record at offset 0) to below p + 1 + 8.
-// Included by mappability.hip behind query_anchor.hpp and query_min_len.hpp.
 #pragma once
 #include "query_anchor.hpp"
 #include "query_min_len.hpp"
@@ -34,15 +33,7 @@ __global__ void __launch_bounds__(256) k_qminlen_end(FmView f, const u8* q, cons
                                                     u32 t, u64 p0, u64 p1, u32* out, QminlenCounters* ctr) {
   const u64 i = p0 + (u64)blockIdx.x * blockDim.x + threadIdx.x;
   AnchLane c;
-  c.pat = q;
-  c.p = i;
-  c.k = min_k;
-  c.rev = false;
-  c.W = W;
-  c.cap = t + 1;
-  c.total = 0;
-  c.steps = c.tab = c.rows = 0;
-  c.t0 = c.t1 = 0;
+  mm_lane_init(c, q, i, min_k, W, t + 1);
   u32 ok = 0, probes = 0;
   if (i < p1) {
     // limit(p): the last byte that is not A/C/G/T at or in front of p, no further than max_k away
@@ -64,7 +55,8 @@ __global__ void __launch_bounds__(256) k_qminlen_end(FmView f, const u8* q, cons
       ok = 1;
       v = 0;
       const u32 strands = forward_only ? 1u : 2u;
-      // lo fails (min_k - 1: nothing to probe there), hi passes once the first probe, at lim, has; step 0 marks that first probe
+      // k_qminlen's probe loop, spelled out a second time on purpose: shared as a helper it compiles differently ("One
+      // search, folded").  lo fails (min_k - 1: nothing to probe there), hi passes once the first probe, at lim, has; step 0 marks that first probe
       u32 lo = min_k - 1, hi = lim, step = 0, k = lim;
 #pragma nounroll
       for (;;) {  // (a loop: one copy of the search in the kernel)
@@ -73,10 +65,8 @@ __global__ void __launch_bounds__(256) k_qminlen_end(FmView f, const u8* q, cons
         c.total = 0;
 #pragma nounroll
         for (u32 s = 0; s < strands && c.total < c.cap; ++s) {
-          c.rev = s != 0;
-          c.t0 = s ? k - anchor : 0u;  // step t consumes pattern index k-1-t: w's last a bases are revcomp(w)'s first a
-          c.t1 = s ? k : anchor;
-          anch_strand<E>(f, c);
+          mm_set_strand(c, s != 0, anchor);
+          mm_strand<E>(f, c);
         }
         ++probes;
         const bool pass = c.total <= t;
@@ -100,9 +90,7 @@ __global__ void __launch_bounds__(256) k_qminlen_end(FmView f, const u8* q, cons
   }
   wave_add(&ctr->valid, ok);  // (every lane of the wavefront is here)
   wave_add(&ctr->probes, probes);
-  wave_add(&ctr->steps, c.steps);
-  wave_add(&ctr->table_reads, c.tab);
-  wave_add(&ctr->verified_rows, c.rows);
+  mm_flush(ctr, c);
 }
 
 }  // namespace dg
