@@ -39,6 +39,7 @@
 #include "hunt_select.hpp"
 #include "hunt_locate.hpp"
 #include "hunt_verify.hpp"
+#include "hunt_batch.hpp"
 
 namespace dg {
 
@@ -420,81 +421,155 @@ static PinnedPool& pinned_pool() {
   static PinnedPool* P = new PinnedPool;  // leaked on purpose
   return *P;
 }
+struct BlockGuard {  // the block of the speculative fetch, laid out for capn hits: hands an unused block back on every early return
+  PinnedBlock* pb = nullptr;
+  u64 capn = 0;
+  ~BlockGuard() {
+    if (pb) pinned_pool().put(pb);
+  }
+};
 
-// One batch through the five kernels.  All sizes that are only known on the device (number of leaves, number of hits)
-// are handled with capacity guesses that the kernels check themselves; the host synchronises ONCE at the end, and
-// repeats the batch with larger buffers in the rare case a capacity was exceeded.
-// group_counts != nullptr: count mode (`dicey padlock`, padlock.h:396-421) — stop after the select stage and return, per
-// (query, strand), the occurrences summed over the kept neighbourhood strings; no locate, no verify.
-// h_qbytes / h_qoff: the host copy of the queries when the caller has one (needed only when a neighbourhood could reach
-// the cap; read back from the device otherwise).
-int run_batch(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uint32_t nseq, const void* d_qbytes,
-                     const void* d_qoff, size_t nq, u64 total, u32 maxlen, int fetch, dg_hunt_result** out, SearchExtra* sx,
-                     uint64_t* group_counts, const uint8_t* h_qbytes, const uint64_t* h_qoff) {
+// ------------------------------------------------------------------------------------------------------------
+// run_batch's stages, in the order a batch runs them (types: hunt_batch.hpp)
+// ------------------------------------------------------------------------------------------------------------
+
+// queries above MAX_QLEN take the banded long-query verify (k_verify_long); alignment lengths are 16-bit in dg_hit
+static constexpr u32 LONG_QLEN_MAX = 30000;
+static constexpr u32 TB = 256;
+static_assert(EV_COUNT == sizeof(dg_index::ev) / sizeof(hipEvent_t), "one name per event of the handle");
+
+// What is fixed for the batch, and the three limits of the envelope
+static int make_plan(BatchPlan& pl, const dg_switches& sw, const dg_hunt_params* p, u32 nseq, const void* d_qbytes, const void* d_qoff, size_t nq,
+                     u64 total, u32 maxlen, int fetch, SearchExtra* sx, uint64_t* group_counts, const uint64_t* h_qoff) {
   if (nseq == 0) return fail(DG_EINVAL, "no reference sequences");
-  const bool indel = !p->hamming;
-  // queries above MAX_QLEN take the banded long-query verify (k_verify_long); alignment lengths are 16-bit in dg_hit
-  static constexpr u32 LONG_QLEN_MAX = 30000;
   if (maxlen > LONG_QLEN_MAX) return fail(DG_ELIMIT, "query of %u nt exceeds the supported maximum of %u", maxlen, LONG_QLEN_MAX);
   u32 dmax_eff = p->distance;
   if (maxlen >= 1 && dmax_eff >= maxlen) dmax_eff = maxlen - 1;
   if (dmax_eff > DMAX) return fail(DG_ELIMIT, "distance %u exceeds the supported maximum of %u", p->distance, DMAX);
-  DG_HIP(hipSetDevice(ix->device));
+  pl.p = p;
+  pl.nseq = nseq;
+  pl.d_qbytes = d_qbytes;
+  pl.d_qoff = d_qoff;
+  pl.nq = nq;
+  pl.total = total;
+  pl.maxlen = maxlen;
+  pl.caller_qoff = h_qoff;
+  pl.sx = sx;
+  pl.group_counts = group_counts;
+  pl.fetch = fetch;
+  pl.hunt = !sx && !group_counts;
+  pl.indel = !p->hamming;
+  pl.dmax_eff = dmax_eff;
+  pl.ngrp = 2 * (u64)nq;
+  pl.packed = maxlen + dmax_eff <= PACK_MAX_LEN;
+  pl.band_verify = !sw.no_band && pl.hunt && maxlen <= 32 && dmax_eff <= 2;  // (test switches are read per batch: the GPU suite flips them inside one process)
+  pl.stride = pl.band_verify ? 0u : ((maxlen + 3 * dmax_eff) + maxlen + 8 + 7) & ~7u;
+  pl.ops_per_hit = dmax_eff;
+  pl.compact = (p->flags & DG_HUNT_COMPACT) && pl.hunt;
+  pl.chit_words = 2u + pl.ops_per_hit;
+  pl.phase_events = (p->flags & DG_HUNT_PHASE_TIMES) != 0 || !pl.hunt;
+  pl.scan_tmp = pl.ngrp / SCAN_CHUNK + pl.ngrp / (SCAN_CHUNK * SCAN_CHUNK) + 64;
+  return DG_OK;
+}
+
+// Cap stage, upload: modes and the host's explicit patterns into WS_XS, with room for what k_cap_enum can append
+static int upload_xs(dg_index* ix, const BatchPlan& pl, const CapScan& cs, u64 dev_strings, u64 dev_bytes, CapResult& cr) {
   hipStream_t st = ix->stream;
-  const dg_switches& sw = ix->sw;  // the environment switches, read by the entry point on the caller's thread
-  const bool host_timing = sw.host_timing;  // host phases of every batch to stderr
-  // HIP events between the stages (ms_select / ms_locate / ms_verify of the result) only on request: every record is a marker packet
-  // the next kernel waits behind; the batch's total and the flat search kernel's time are always measured (four events)
-  const bool phase_events = (p->flags & DG_HUNT_PHASE_TIMES) != 0 || sx || group_counts;
-  const double t_enter = host_timing ? host_us() : 0.0;
-  double t_launched = 0, t_synced = 0;
-  for (int i = 0; i < 9; ++i)
-    if (!ix->ev[i]) DG_HIP(hipEventCreate(&ix->ev[i]));
-  auto& ws = ix->ws;
-  const u64 ngrp = 2 * (u64)nq;
-  const u32 TB = 256;
-  const bool packed = maxlen + dmax_eff <= PACK_MAX_LEN;  // every neighbourhood string fits 128 bits
-  // Alignment rows.  The banded verify writes a row front to back, and a row it keeps has the query's characters plus at most d
-  // gap columns inside the query (leading and trailing query-gap columns are stripped, hunter.h:391-401, and an optimal path has
-  // score >= -d): maxlen + d bytes, rounded up to the 64-bit words it stores.  The other verify kernels build the row from the
-  // end of a buffer twice as long.  (r02: 56 -> 24 bytes per row for 20-mers — what travels to the host and over xGMI.)
-  const bool no_band = sw.no_band;  // (test switches are read per batch: the GPU suite flips them inside one process)
-  const bool band_verify = !no_band && !sx && !group_counts && maxlen <= 32 && dmax_eff <= 2;
-  // scratch rows of the full-matrix kernels (built from the end of a buffer twice the row length); the banded kernel needs none
-  const u32 stride = band_verify ? 0u : ((maxlen + 3 * dmax_eff) + maxlen + 8 + 7) & ~7u;
-  const u32 ops_per_hit = dmax_eff;  // compact alignment description: at most |score| <= d columns are not a match
-  // ABI 5: results as compact records (position, meta, ops) + one word per query, in ONE device block [qhits | qinfo | records]
-  // that a single copy brings to the host — no pack kernel, 12 instead of 24 bytes per hit at distance 1
-  const bool compact = (p->flags & DG_HUNT_COMPACT) && !sx && !group_counts;
-  const u32 chit_words = 2u + ops_per_hit;
-  const u64 scan_tmp = ngrp / SCAN_CHUNK + ngrp / (SCAN_CHUNK * SCAN_CHUNK) + 64;
-  DG_TRY(ws[WS_FW].reserve(total + 8));
-  DG_TRY(ws[WS_RV].reserve(total + 8));
-  DG_TRY(ws[WS_QSEQ].reserve(total + 8));
-  DG_TRY(ws[WS_QMETA].reserve(nq * 16 + 64));
-  DG_TRY(ws[WS_GINFO].reserve(ngrp * (sizeof(GidInfo) + sizeof(uint4)) + 64));
-  DG_TRY(ws[WS_GRP].reserve((ngrp + 1) * 8 + (nq + 1) * 8 + ngrp * 4 * 3 + nq * 4 + scan_tmp * 8 + sizeof(Counters) + sizeof(Summary) + 512));
-  DG_TRY(ws[WS_CUM].reserve((u64)nseq * 8 + 8));
-  // Could any query of this batch reach the cap?  (the bound grows with the length and with the number of N's)
+  const u64 nxs = cr.nxs;
+  const XsLayout L(pl.nq, cs.xs_bytes.size() + dev_bytes, nxs + dev_strings);
+  DG_TRY(ix->ws[WS_XS].reserve(L.bytes));
+  u8* base = ix->ws[WS_XS].as<u8>();
+  cr.d_qmode = base;
+  cr.d_xs_bytes = base + L.o_bytes;
+  cr.d_xs_off = (u64*)(base + L.o_off);
+  cr.d_xs_gid = (u32*)(base + L.o_gid);
+  DG_HIP(hipMemcpyAsync(cr.d_qmode, cs.mode.data(), pl.nq, hipMemcpyHostToDevice, st));
+  if (nxs) {
+    DG_HIP(hipMemcpyAsync(cr.d_xs_bytes, cs.xs_bytes.data(), cs.xs_bytes.size(), hipMemcpyHostToDevice, st));
+    DG_HIP(hipMemcpyAsync(cr.d_xs_gid, cs.xs_gid.data(), nxs * 4, hipMemcpyHostToDevice, st));
+  }
+  DG_HIP(hipMemcpyAsync(cr.d_xs_off, cs.xs_off.data(), (nxs + 1) * 8, hipMemcpyHostToDevice, st));
+  DG_HIP(hipStreamSynchronize(st));  // the host vectors go out of use only after the copies
+  return DG_OK;
+}
+
+// Cap stage, device enumeration: neighbors() with its cap on the device (hunt_cap.hpp): modes and explicit patterns of the listed
+// queries, before k_prepare reads them.  One host round trip for the pattern count (launch sizes of the batch depend on it).
+static int launch_cap_enum(dg_index* ix, const BatchPlan& pl, const std::vector<u32>& dev_jobs, u64 host_bytes, u64 dev_strings, u64 dev_bytes,
+                           CapResult& cr) {
+  hipStream_t st = ix->stream;
+  const u32 maxlen = pl.maxlen, dmax_eff = pl.dmax_eff;
+  const u32 njobs = (u32)dev_jobs.size();
+  // persistent workgroups; the kernel is chains of atomics and probes per workgroup, so its time falls with the number of
+  // workgroups in flight and the independent accesses each keeps in flight (r04 first form: 512 workgroups, one access at a
+  // time per lane: 46.7 ms per 2 000 25-mers)
+  const u32 nwg = std::min<u32>(njobs, 1024u);  // four per CU fit (113 VGPRs)
+  const u64 leaves = cap::total_leaves(std::min<u32>(maxlen, cap::MAX_KEY_LEN - dmax_eff), dmax_eff) + 2;
+  const u64 distinct = std::min<u64>(leaves, neighbourhood_bound(std::min<u32>(maxlen, cap::MAX_KEY_LEN - dmax_eff), dmax_eff, true, 0));
+  const CapLayout L(nwg, njobs, leaves, distinct);
+  DG_TRY(ix->ws[WS_CAP].reserve(L.bytes));
+  u8* cb = ix->ws[WS_CAP].as<u8>();
+  CapAlloc h_al = {((unsigned long long)cr.nxs << 36) | (unsigned long long)host_bytes, 0u, 0u};
+  DG_HIP(hipMemcpyAsync(cb + L.o_jobs, dev_jobs.data(), (u64)njobs * 4, hipMemcpyHostToDevice, st));
+  DG_HIP(hipMemcpyAsync(cb + L.o_alloc, &h_al, sizeof h_al, hipMemcpyHostToDevice, st));
+  Batch qb{};  // k_cap_enum reads the raw queries only
+  qb.qbytes = (const u8*)pl.d_qbytes;
+  qb.qoff = (const u64*)pl.d_qoff;
+  qb.nq = pl.nq;
+  CapDevArgs ca;
+  ca.jobs = (const u32*)(cb + L.o_jobs);
+  ca.njobs = njobs;
+  ca.tab = (u64*)(cb + L.o_tab);
+  ca.tcap_log2 = L.tcap_log2;
+  ca.ev = (int*)(cb + L.o_ev);
+  ca.evcap = L.evcap;
+  ca.qmode = cr.d_qmode;
+  ca.xs_bytes = cr.d_xs_bytes;
+  ca.xs_off = cr.d_xs_off;
+  ca.xs_gid = cr.d_xs_gid;
+  ca.alloc = (unsigned long long*)(cb + L.o_alloc);
+  ca.cap_strings = cr.nxs + dev_strings;
+  ca.cap_bytes = host_bytes + dev_bytes;
+  ca.status = (u32*)(cb + L.o_alloc + 8);
+  ca.maxsize = pl.p->max_neighborhood;
+  ca.distance = pl.p->distance;
+  ca.reverse = !pl.p->forward_only;
+  hipLaunchKernelGGL(k_cap_enum, dim3(nwg), dim3(256), 0, st, qb, ca);
+  DG_HIP(hipMemcpyAsync(&h_al, cb + L.o_alloc, sizeof h_al, hipMemcpyDeviceToHost, st));
+  DG_HIP(hipStreamSynchronize(st));
+  DG_HIP(hipGetLastError());
+  if (h_al.status & 2u) return fail(DG_EHIP, "internal error: a hash table of the device neighbourhood enumeration overflowed");
+  if (h_al.status & 1u) return fail(DG_EHIP, "internal error: the device neighbourhood enumeration produced more strings than the cap allows");
+  cr.nxs = h_al.alloc >> 36;
+  return DG_OK;
+}
+
+// Cap stage: could any query of this batch reach the cap?  (the bound grows with the length and with the number of N's)  Those that
+// could are enumerated, on the host (cap_scan) or on the device (k_cap_enum), and arrive as explicit patterns.
+// h_qbytes / pl.caller_qoff: the host copy of the queries when the caller has one; read back from the device otherwise — for cap_scan
+// only: the read-back ends with this function, and pl.caller_qoff goes on saying whether the CALLER has the offsets.
+static int cap_stage(dg_index* ix, const BatchPlan& pl, const uint8_t* h_qbytes, CapResult& cr) {
+  hipStream_t st = ix->stream;
+  const dg_switches& sw = ix->sw;
+  const dg_hunt_params* p = pl.p;
+  const size_t nq = pl.nq;
+  const u32 maxlen = pl.maxlen;
   const double t_cap0 = host_us();
   CapScan cs;
   std::vector<u32> dev_jobs;  // queries whose capped neighbourhood is enumerated on the device (k_cap_enum)
-  // the caller's host copy of the offsets (nullptr on the dg_hunt_device path).  The read-back below serves cap_scan only and must not
-  // outlive it: queue_fetch and the result's qoff distinguish "the caller has the offsets" from "pack them on the device" by this.
-  const uint64_t* const caller_qoff = h_qoff;
-  if (maxlen >= 1 && neighbourhood_bound(maxlen, dmax_eff, indel, maxlen) >= p->max_neighborhood) {
+  if (maxlen >= 1 && neighbourhood_bound(maxlen, pl.dmax_eff, pl.indel, maxlen) >= p->max_neighborhood) {
     std::vector<u8> hb;
     std::vector<u64> ho;
     const uint8_t* sb = h_qbytes;
-    const uint64_t* so = h_qoff;
+    const uint64_t* so = pl.caller_qoff;
     if (!sb || !so) {
-      hb.resize(total + 1);
+      hb.resize(pl.total + 1);
       ho.resize(nq + 1);
-      if (total) DG_HIP(hipMemcpyAsync(hb.data(), d_qbytes, total, hipMemcpyDeviceToHost, st));
-      DG_HIP(hipMemcpyAsync(ho.data(), d_qoff, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+      if (pl.total) DG_HIP(hipMemcpyAsync(hb.data(), pl.d_qbytes, pl.total, hipMemcpyDeviceToHost, st));
+      DG_HIP(hipMemcpyAsync(ho.data(), pl.d_qoff, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
       DG_HIP(hipStreamSynchronize(st));
       // read back from the device, so never seen by a host pass: cap_scan indexes with them
-      if (ho[nq] != total) return fail(DG_EINVAL, "dg_hunt_device: total_qbytes does not match qoff[nq]");
+      if (ho[nq] != pl.total) return fail(DG_EINVAL, "dg_hunt_device: total_qbytes does not match qoff[nq]");
       for (size_t i = 0; i < nq; ++i)
         if (ho[i + 1] < ho[i] || ho[i + 1] - ho[i] > maxlen)
           return fail(DG_EINVAL, "dg_hunt_device: qoff decreases at query %zu, or the query exceeds the %u nt this batch was sized for", i, maxlen);
@@ -502,112 +577,50 @@ int run_batch(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uin
       so = ho.data();
     }
     // DICEY_CAP_HOST: every capped neighbourhood on the host (nbhd_host.hpp), as before r04 — the GPU suite runs both
-    DG_TRY(cap_scan(sb, so, nq, p, group_counts != nullptr, cs, sw, sw.cap_host ? nullptr : &dev_jobs));
+    DG_TRY(cap_scan(sb, so, nq, p, pl.group_counts != nullptr, cs, sw, sw.cap_host ? nullptr : &dev_jobs));
   }
-  u64 nxs = cs.xs_gid.size();
-  if (nxs >= 0x0FFFFFFFull || cs.xs_bytes.size() > (48ull << 30))
-    return fail(DG_ELIMIT, "%llu explicit neighbourhood strings in one batch; pass fewer sequences per call", (unsigned long long)nxs);
+  cr.nxs = cs.xs_gid.size();
+  if (cr.nxs >= 0x0FFFFFFFull || cs.xs_bytes.size() > (48ull << 30))
+    return fail(DG_ELIMIT, "%llu explicit neighbourhood strings in one batch; pass fewer sequences per call", (unsigned long long)cr.nxs);
   // room for what k_cap_enum can append: <= max(maxsize, 1) strings of <= maxlen + d characters per strand of its queries
   const u64 dev_strings = dev_jobs.size() * (p->forward_only ? 1ull : 2ull) * std::max<u64>(p->max_neighborhood, 1);
-  const u64 dev_bytes = dev_strings * (maxlen + dmax_eff);
+  const u64 dev_bytes = dev_strings * (maxlen + pl.dmax_eff);
   if (!dev_jobs.empty()) {
     u64 budget = 24ull << 30;
     if (sw.cap_budget_mb) budget = sw.cap_budget_mb << 20;
-    if (dev_bytes + dev_strings * 12 > budget || nxs + dev_strings >= 0x0FFFFFFFull)
+    if (dev_bytes + dev_strings * 12 > budget || cr.nxs + dev_strings >= 0x0FFFFFFFull)
       return fail(DG_ELIMIT, "%zu of the %zu sequences of this call can reach the maxNeighborhood cap (%u); their explicit neighbourhoods may need "
                   "%llu MB of device memory (budget %llu MB): pass fewer sequences per call", dev_jobs.size(), nq, p->max_neighborhood,
                   (unsigned long long)((dev_bytes + dev_strings * 12) >> 20), (unsigned long long)(budget >> 20));
   }
-  u8* d_qmode = nullptr;
-  u8* d_xs_bytes = nullptr;
-  u64* d_xs_off = nullptr;
-  u32* d_xs_gid = nullptr;
-  if (!cs.mode.empty()) {
-    const u64 a0 = (nq + 63) & ~63ull, a1 = a0 + ((cs.xs_bytes.size() + dev_bytes + 63) & ~63ull), a2 = a1 + (nxs + dev_strings + 1) * 8,
-              a3 = a2 + (nxs + dev_strings) * 4;
-    DG_TRY(ws[WS_XS].reserve(a3 + 64));
-    u8* base = ws[WS_XS].as<u8>();
-    d_qmode = base;
-    d_xs_bytes = base + a0;
-    d_xs_off = (u64*)(base + a1);
-    d_xs_gid = (u32*)(base + a2);
-    DG_HIP(hipMemcpyAsync(d_qmode, cs.mode.data(), nq, hipMemcpyHostToDevice, st));
-    if (nxs) {
-      DG_HIP(hipMemcpyAsync(d_xs_bytes, cs.xs_bytes.data(), cs.xs_bytes.size(), hipMemcpyHostToDevice, st));
-      DG_HIP(hipMemcpyAsync(d_xs_gid, cs.xs_gid.data(), nxs * 4, hipMemcpyHostToDevice, st));
-    }
-    DG_HIP(hipMemcpyAsync(d_xs_off, cs.xs_off.data(), (nxs + 1) * 8, hipMemcpyHostToDevice, st));
-    DG_HIP(hipStreamSynchronize(st));  // the host vectors go out of use only after the copies
-  }
-  if (!dev_jobs.empty()) {
-    // neighbors() with its cap on the device (hunt_cap.hpp): modes and explicit patterns of the listed queries, before k_prepare
-    // reads them.  One host round trip for the pattern count (launch sizes below depend on it).
-    const u32 njobs = (u32)dev_jobs.size();
-    // persistent workgroups; the kernel is chains of atomics and probes per workgroup, so its time falls with the number of
-    // workgroups in flight and the independent accesses each keeps in flight (r04 first form: 512 workgroups, one access at a
-    // time per lane: 46.7 ms per 2 000 25-mers)
-    const u32 nwg = std::min<u32>(njobs, 1024u);  // four per CU fit (113 VGPRs)
-    const u64 leaves = cap::total_leaves(std::min<u32>(maxlen, cap::MAX_KEY_LEN - dmax_eff), dmax_eff) + 2;
-    // table slots: twice the number of DISTINCT strings a strand can hold (neighbourhood_bound; 15 705 for a 25-mer at distance 2
-    // against 20 201 leaves) — 512 KB per strand instead of 1 MB for 25-mers
-    const u64 distinct = std::min<u64>(leaves, neighbourhood_bound(std::min<u32>(maxlen, cap::MAX_KEY_LEN - dmax_eff), dmax_eff, true, 0));
-    u32 tcap_log2 = 8;
-    while ((1ull << tcap_log2) < 2 * distinct) ++tcap_log2;
-    const u32 evcap = (u32)((leaves + 2 + 63) & ~63ull);
-    const u64 o_tab = 0, o_ev = o_tab + (u64)nwg * 2 * (16ull << tcap_log2), o_jobs = o_ev + (u64)nwg * 2 * evcap * 4,
-              o_alloc = (o_jobs + (u64)njobs * 4 + 63) & ~63ull, o_end = o_alloc + 64;
-    DG_TRY(ws[WS_CAP].reserve(o_end));
-    u8* cb = ws[WS_CAP].as<u8>();
-    struct {
-      unsigned long long alloc;
-      u32 status, pad;
-    } h_al = {((unsigned long long)nxs << 36) | (unsigned long long)cs.xs_bytes.size(), 0u, 0u};
-    DG_HIP(hipMemcpyAsync(cb + o_jobs, dev_jobs.data(), (u64)njobs * 4, hipMemcpyHostToDevice, st));
-    DG_HIP(hipMemcpyAsync(cb + o_alloc, &h_al, sizeof h_al, hipMemcpyHostToDevice, st));
-    Batch qb{};  // k_cap_enum reads the raw queries only
-    qb.qbytes = (const u8*)d_qbytes;
-    qb.qoff = (const u64*)d_qoff;
-    qb.nq = nq;
-    CapDevArgs ca;
-    ca.jobs = (const u32*)(cb + o_jobs);
-    ca.njobs = njobs;
-    ca.tab = (u64*)(cb + o_tab);
-    ca.tcap_log2 = tcap_log2;
-    ca.ev = (int*)(cb + o_ev);
-    ca.evcap = evcap;
-    ca.qmode = d_qmode;
-    ca.xs_bytes = d_xs_bytes;
-    ca.xs_off = d_xs_off;
-    ca.xs_gid = d_xs_gid;
-    ca.alloc = (unsigned long long*)(cb + o_alloc);
-    ca.cap_strings = nxs + dev_strings;
-    ca.cap_bytes = cs.xs_bytes.size() + dev_bytes;
-    ca.status = (u32*)(cb + o_alloc + 8);
-    ca.maxsize = p->max_neighborhood;
-    ca.distance = p->distance;
-    ca.reverse = !p->forward_only;
-    hipLaunchKernelGGL(k_cap_enum, dim3(nwg), dim3(256), 0, st, qb, ca);
-    DG_HIP(hipMemcpyAsync(&h_al, cb + o_alloc, sizeof h_al, hipMemcpyDeviceToHost, st));
-    DG_HIP(hipStreamSynchronize(st));
-    DG_HIP(hipGetLastError());
-    if (h_al.status & 2u) return fail(DG_EHIP, "internal error: a hash table of the device neighbourhood enumeration overflowed");
-    if (h_al.status & 1u) return fail(DG_EHIP, "internal error: the device neighbourhood enumeration produced more strings than the cap allows");
-    nxs = h_al.alloc >> 36;
-  }
-  const double ms_cap = (cs.mode.empty() && dev_jobs.empty()) ? 0.0 : (host_us() - t_cap0) * 1e-3;
-  Batch b;
+  if (!cs.mode.empty()) DG_TRY(upload_xs(ix, pl, cs, dev_strings, dev_bytes, cr));
+  if (!dev_jobs.empty()) DG_TRY(launch_cap_enum(ix, pl, dev_jobs, cs.xs_bytes.size(), dev_strings, dev_bytes, cr));
+  cr.dev_queries = dev_jobs.size();
+  cr.looked_at = cs.looked_at;
+  cr.ms_cap = (cs.mode.empty() && dev_jobs.empty()) ? 0.0 : (host_us() - t_cap0) * 1e-3;
+  return DG_OK;
+}
+
+// The batch's fixed device pointers (the per-attempt ones: reserve_attempt) and which flat kernels it qualifies for
+static void init_batch(dg_index* ix, const BatchPlan& pl, const CapResult& cr, const GrpLayout& gl, BatchBufs& bf) {
+  auto& ws = ix->ws;
+  const dg_switches& sw = ix->sw;
+  const dg_hunt_params* p = pl.p;
+  const u64 nq = pl.nq, ngrp = pl.ngrp;
+  const u32 maxlen = pl.maxlen, dmax_eff = pl.dmax_eff;
+  Batch& b = bf.b;
   b.fastK = (dmax_eff == 1 && ix->view.K && maxlen > ix->view.K && ngrp * (u64)std::min(maxlen, 31u) * 9 < 0xFFFFFF00ull && ngrp < (1u << 24)) ? ix->view.K : 0u;
   // (r05: Hamming distance 2 as well — the same kernel with "no edit" in place of the deletions)
-  b.fast2K = (dmax_eff == 2 && (indel || !sw.no_flat_ham2) && ix->view.K && maxlen >= ix->view.K + 2 && ngrp < 0x7FFFFFFFull) ? ix->view.K : 0u;
+  b.fast2K = (dmax_eff == 2 && (pl.indel || !sw.no_flat_ham2) && ix->view.K && maxlen >= ix->view.K + 2 && ngrp < 0x7FFFFFFFull) ? ix->view.K : 0u;
   b.tabK = sw.no_nwin ? 0u : ix->view.K;
   b.nrun_min = ((dmax_eff == 1 || dmax_eff == 2) && ngrp < 0x7FFFFFFFull) ? ix->view.nrun_min : 0u;  // (non-zero: k_nres is launched with the generic kernels)
-  b.qmode = d_qmode;
-  b.xs_bytes = d_xs_bytes;
-  b.xs_off = d_xs_off;
-  b.xs_gid = d_xs_gid;
-  b.nxs = nxs;
-  b.qbytes = (const u8*)d_qbytes;
-  b.qoff = (const u64*)d_qoff;
+  b.qmode = cr.d_qmode;
+  b.xs_bytes = cr.d_xs_bytes;
+  b.xs_off = cr.d_xs_off;
+  b.xs_gid = cr.d_xs_gid;
+  b.nxs = bf.nxs = cr.nxs;
+  b.qbytes = (const u8*)pl.d_qbytes;
+  b.qoff = (const u64*)pl.d_qoff;
   b.nq = nq;
   b.fw = ws[WS_FW].as<u8>();
   b.rv = ws[WS_RV].as<u8>();
@@ -619,702 +632,650 @@ int run_batch(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uin
   b.qnondna = meta + 3 * nq;
   b.qinfo = nullptr;  // set per attempt (the compact block may move when the hit capacity grows)
   b.distance = p->distance;
-  b.indel = indel;
+  b.indel = pl.indel;
   b.reverse = !p->forward_only;
   b.max_locations = p->max_locations;
   b.max_neighborhood = p->max_neighborhood;
   b.ginfo = ws[WS_GINFO].as<GidInfo>();
   b.gpeq = reinterpret_cast<uint4*>(ws[WS_GINFO].as<GidInfo>() + ngrp);  // (GidInfo is 16 bytes: the masks stay 16-byte aligned)
-  u8* gp = ws[WS_GRP].as<u8>();
-  u64* grp_off = (u64*)gp;
-  gp += (ngrp + 1) * 8;
-  u64* hit_off = (u64*)gp;
-  gp += (nq + 1) * 8;
-  u64* scan_buf = (u64*)gp;
-  gp += scan_tmp * 8;
-  gp = (u8*)(((uintptr_t)gp + 63) & ~(uintptr_t)63);
-  // counters, device-side summary, group counts and selection counts sit next to each other: one memset clears them
-  u8* const zero_from = gp;
-  Counters* ctr = (Counters*)gp;
-  gp += (sizeof(Counters) + 63) & ~(size_t)63;
-  u32* grp_cnt = (u32*)gp;
-  gp += ngrp * 4;
-  u32* nsel = (u32*)gp;
-  gp += ngrp * 4;
-  const size_t zero_bytes = (size_t)(gp - zero_from);
-  u32* selbase = (u32*)gp;  // first Sel slot of the groups k_search1s serves (set by k_prepare / k_search1s)
-  gp += ngrp * 4;
-  b.refused = &ctr->pad_[1];
-  b.too_long = &ctr->pad_[2];
-  b.nwin = &ctr->pad_[7];
-  b.short2 = &ctr->pad_[9];
+  void* gp = ws[WS_GRP].p;
+  bf.grp_off = gl.grp_off(gp);
+  bf.hit_off = gl.hit_off(gp);
+  bf.scan_buf = gl.scan_buf(gp);
+  bf.ctr = gl.ctr(gp);
+  bf.grp_cnt = gl.grp_cnt(gp);
+  bf.nsel = gl.nsel(gp);
+  bf.selbase = gl.selbase(gp);
+  bf.qhits = gl.qhits(gp);
+  b.refused = &bf.ctr->pad_[CW_REFUSED];
+  b.too_long = &bf.ctr->pad_[CW_TOO_LONG];
+  b.nwin = &bf.ctr->pad_[CW_N_NWIN];
+  b.short2 = &bf.ctr->pad_[CW_N_SHORT2];
   b.fast2_minlen = 0;
   b.maxlen_bound = maxlen;
-  b.total_qbytes = total;
-  u32* qhits = (u32*)gp;  // (compact results: re-pointed into the compact block, per attempt)
-  if (!ix->pinned) DG_HIP(hipHostMalloc((void**)&ix->pinned, 4096, 0));
-  Summary& hsum = *(Summary*)ix->pinned;
-  std::vector<u64> cum(nseq);
+  b.total_qbytes = pl.total;
+}
+
+// cumulative sequence starts: kept for the result (seq_start), uploaded when they changed (sequence lengths rarely do between batches)
+static int upload_seq_starts(dg_index* ix, const uint32_t* seqlen, std::vector<u64>& cum) {
   u64 run = 0;
-  for (u32 r = 0; r < nseq; ++r) {
+  for (size_t r = 0; r < cum.size(); ++r) {
     cum[r] = run;
     run += seqlen[r];
   }
-  if (cum != ix->cum_cache) {  // sequence lengths rarely change between batches
-    DG_HIP(hipMemcpyAsync(ws[WS_CUM].p, cum.data(), (u64)nseq * 8, hipMemcpyHostToDevice, st));
-    DG_HIP(hipStreamSynchronize(st));
+  if (cum != ix->cum_cache) {
+    DG_HIP(hipMemcpyAsync(ix->ws[WS_CUM].p, cum.data(), (u64)cum.size() * 8, hipMemcpyHostToDevice, ix->stream));
+    DG_HIP(hipStreamSynchronize(ix->stream));
     ix->cum_cache = cum;
   }
+  return DG_OK;
+}
 
-  u32 base_gen = 0;
-  hipEvent_t base_ev = nullptr;
-  if (dg_index::SharedHints* sh = ix->shared_hints.load()) {  // what the handle's other lanes have learnt since this lane's previous batch
-    std::lock_guard<std::mutex> lk(sh->mu);
-    // the lanes' common timeline: this lane's stream is idle here (its previous batch has been synchronised), so a base recorded on it
-    // completes at once; the other base stays valid for the other lanes' batches in flight
-    const double now = host_us();
-    if (!sh->base_gen || now - sh->base_host_us > 4e6) {
-      const u32 g = sh->base_gen + 1;
-      if (!sh->ev_base[g & 1] && hipEventCreate(&sh->ev_base[g & 1]) != hipSuccess) sh->ev_base[g & 1] = nullptr;
-      if (sh->ev_base[g & 1] && hipEventRecord(sh->ev_base[g & 1], st) == hipSuccess) {
-        sh->base_gen = g;
-        sh->base_host_us = now;
-      }
-    }
-    base_gen = sh->base_gen;
-    base_ev = base_gen ? sh->ev_base[base_gen & 1] : nullptr;
-    if (sh->valid) {
-      ix->shard_cap_hint = std::max(ix->shard_cap_hint, sh->shard_cap);
-      ix->flat_cap_hint = std::max(ix->flat_cap_hint, sh->flat_cap);
-      ix->hit_cap_hint = std::max(ix->hit_cap_hint, sh->hit_cap);
-      if (sh->fetch_hits) ix->fetch_hits_hint = sh->fetch_hits;  // (the most recent batch's, like the two below)
-      ix->generic_sticky = std::max(ix->generic_sticky, sh->generic_sticky);
-      ix->jobs_sticky = std::max(ix->jobs_sticky, sh->jobs_sticky);
-      ix->generic_hint = ix->generic_sticky > 0;
-      ix->jobs_hint = ix->jobs_sticky > 0;
-      ix->jobs_big_hint = sh->jobs_big;
-      ix->fused_leaves_hint = sh->fused_leaves;
+// The lanes' common record, read when a batch starts and written when it ends (the two functions list the same fields).
+// pull: what the handle's other lanes have learnt since this lane's previous batch, and the base event of the lanes' common timeline
+static void pull_shared_hints(dg_index* ix, u32& base_gen, hipEvent_t& base_ev) {
+  dg_index::SharedHints* sh = ix->shared_hints.load();
+  if (!sh) return;
+  std::lock_guard<std::mutex> lk(sh->mu);
+  // the lanes' common timeline: this lane's stream is idle here (its previous batch has been synchronised), so a base recorded on it
+  // completes at once; the other base stays valid for the other lanes' batches in flight
+  const double now = host_us();
+  if (!sh->base_gen || now - sh->base_host_us > 4e6) {
+    const u32 g = sh->base_gen + 1;
+    if (!sh->ev_base[g & 1] && hipEventCreate(&sh->ev_base[g & 1]) != hipSuccess) sh->ev_base[g & 1] = nullptr;
+    if (sh->ev_base[g & 1] && hipEventRecord(sh->ev_base[g & 1], ix->stream) == hipSuccess) {
+      sh->base_gen = g;
+      sh->base_host_us = now;
     }
   }
-  u32 shard_cap = std::max<u32>(ix->shard_cap_hint, (u32)std::max<u64>(64, (16 * (u64)nq + nxs / 8) / NSHARD));
-  u64 hit_cap = std::max<u64>(ix->hit_cap_hint, 4 * (u64)nq + 1024);
+  base_gen = sh->base_gen;
+  base_ev = base_gen ? sh->ev_base[base_gen & 1] : nullptr;
+  if (!sh->valid) return;
+  ix->shard_cap_hint = std::max(ix->shard_cap_hint, sh->shard_cap);
+  ix->flat_cap_hint = std::max(ix->flat_cap_hint, sh->flat_cap);
+  ix->hit_cap_hint = std::max(ix->hit_cap_hint, sh->hit_cap);
+  if (sh->fetch_hits) ix->fetch_hits_hint = sh->fetch_hits;  // (the most recent batch's, like the two below)
+  ix->generic_sticky = std::max(ix->generic_sticky, sh->generic_sticky);
+  ix->jobs_sticky = std::max(ix->jobs_sticky, sh->jobs_sticky);
+  ix->generic_hint = ix->generic_sticky > 0;
+  ix->jobs_hint = ix->jobs_sticky > 0;
+  ix->jobs_big_hint = sh->jobs_big;
+  ix->fused_leaves_hint = sh->fused_leaves;
+}
+// push: for the other lanes' next batches
+static void push_shared_hints(dg_index* ix) {
+  dg_index::SharedHints* sh = ix->shared_hints.load();
+  if (!sh) return;
+  std::lock_guard<std::mutex> lk(sh->mu);
+  sh->shard_cap = std::max(sh->shard_cap, ix->shard_cap_hint);
+  sh->flat_cap = std::max(sh->flat_cap, ix->flat_cap_hint);
+  sh->hit_cap = std::max(sh->hit_cap, ix->hit_cap_hint);
+  sh->fetch_hits = ix->fetch_hits_hint;
+  sh->generic_sticky = ix->generic_sticky;
+  sh->jobs_sticky = ix->jobs_sticky;
+  sh->jobs_big = ix->jobs_big_hint;
+  sh->fused_leaves = ix->fused_leaves_hint;
+  sh->valid = true;
+}
+// The flat search kernel's interval on the lanes' common timeline (dg_hunt_result::t_search_*).  The two base events are used in
+// turn and re-recorded under the shared record's mutex: a batch that outlived two generations (cap-prone or very long batches)
+// finds its base re-recorded and reports no interval rather than a wrong one
+static void search_interval(dg_index* ix, u32 base_gen, hipEvent_t base_ev, dg_hunt_result* R) {
+  dg_index::SharedHints* shb = ix->shared_hints.load();
+  std::unique_lock<std::mutex> lkb(shb->mu);
+  float t0 = 0.f, t1 = 0.f;
+  if (shb->base_gen - base_gen < 2 && hipEventElapsedTime(&t0, base_ev, ix->ev[EV_PREPARED]) == hipSuccess &&
+      hipEventElapsedTime(&t1, base_ev, ix->ev[EV_FLAT_END]) == hipSuccess && t0 >= 0.f) {
+    R->t_search_begin_ms = t0;
+    R->t_search_end_ms = t1;
+    R->t_base_gen = base_gen;
+  }
+}
+
+// The capacities the first attempt starts from: what was enough for the handle's previous batch, or an estimate from the batch's size
+static void start_caps(const dg_index* ix, const BatchPlan& pl, u64 nxs, Attempt& at) {
+  const u64 nq = pl.nq;
+  at.shard_cap = std::max<u32>(ix->shard_cap_hint, (u32)std::max<u64>(64, (16 * nq + nxs / 8) / NSHARD));
+  at.hit_cap = std::max<u64>(ix->hit_cap_hint, 4 * nq + 1024);
   // slices of the flat Sel region (k_search1s): what the previous batch's fullest slice needed plus a quarter — kept strings are a
   // third of the leaf estimate above, and k_locate walks every slot of the region
-  u32 flat_req = ix->flat_cap_hint ? ix->flat_cap_hint : shard_cap;
-  if (sw.debug_caps) {  // tests: start from tiny capacities to exercise the retry path
-    const char* e = sw.debug_caps_s.c_str();
-    shard_cap = (u32)std::max(1, std::atoi(e));
-    hit_cap = (u64)std::max(1, std::atoi(e));
-    flat_req = shard_cap;
+  at.flat_req = ix->flat_cap_hint ? ix->flat_cap_hint : at.shard_cap;
+  if (ix->sw.debug_caps) {  // tests: start from tiny capacities to exercise the retry path
+    const char* e = ix->sw.debug_caps_s.c_str();
+    at.shard_cap = (u32)std::max(1, std::atoi(e));
+    at.hit_cap = (u64)std::max(1, std::atoi(e));
+    at.flat_req = at.shard_cap;
   }
-  u64 nleaf = 0, nhits = 0;
-  bool force_generic = false, force_jobs = false, force_short2 = false;
-  u64 walk_cap = 0;  // room of the walker's group list (k_walk_list)
-  u32 flat_form = 0;  // which flat search kernel the (last) attempt launched: dg_hunt_result::flat_kernel_form
-  u32 verify_form = 0;  // ... and which k_verify_memo instantiation: dg_hunt_result::verify_kernel_form
-  // Fetched results: one pinned block from the pool (pageable copies run at a fraction of the link's speed, and a fresh
-  // hipHostMalloc per batch costs more than the copies), laid out for `capn` hits:
-  // [hit_off | qoff | qdistance qflags qnondna | qseq | hits | ops].  When the previous fetched batch on this handle tells how many
-  // hits to expect, the copies are queued BEHIND the batch's kernels, before its one synchronisation (no second round trip);
-  // a batch with more hits than expected copies again after the synchronisation.
-  struct FetchLayout {
-    u64 o_hit_off, o_qoff, o_meta, o_qseq, o_hits, o_ops, bytes;
-  };
-  auto fetch_layout = [&](u64 capn) {
-    FetchLayout L;
-    if (compact) {  // [hit_off (filled on the host) | qhits | qinfo | records]; o_qoff = qhits, o_meta = qinfo, o_hits = records
-      L.o_hit_off = 0;
-      L.o_qoff = (nq + 1) * 8;
-      L.o_meta = L.o_qoff + (u64)nq * 4;
-      L.o_qseq = L.o_meta + (u64)nq * 4;
-      L.o_hits = L.o_qseq;
-      L.o_ops = L.o_hits + capn * (u64)chit_words * 4;
-      L.bytes = L.o_ops + 64;
-      return L;
-    }
-    L.o_hit_off = 0;
-    L.o_qoff = L.o_hit_off + (nq + 1) * 8;
-    L.o_meta = L.o_qoff + (nq + 1) * 8;
-    L.o_qseq = L.o_meta + 3 * (u64)nq * 4;
-    L.o_hits = (L.o_qseq + total + 15) & ~15ull;
-    L.o_ops = (L.o_hits + capn * sizeof(dg_hit) + 15) & ~15ull;
-    L.bytes = L.o_ops + capn * (u64)ops_per_hit * 4 + 64;
-    return L;
-  };
-  struct BlockGuard {  // hands an unused block back on every early return
-    PinnedBlock* pb = nullptr;
-    ~BlockGuard() {
-      if (pb) pinned_pool().put(pb);
-    }
-  } spec;
-  u64 spec_cap = 0;
-  auto queue_fetch = [&](PinnedBlock* pb, u64 capn) -> int {
-    const FetchLayout L = fetch_layout(capn);
-    if (compact) {  // the device block already has the host layout behind hit_off
-      DG_HIP(hipMemcpyAsync((u8*)pb->p + L.o_qoff, ws[WS_PACK].p, L.o_ops - L.o_qoff, hipMemcpyDeviceToHost, st));
-      return DG_OK;
-    }
-    DG_TRY(ws[WS_PACK].reserve(L.bytes + 64));
-    PackArgs pa;
-    const u32* srcs[6] = {reinterpret_cast<const u32*>(ws[WS_GRP].as<u8>() + (ngrp + 1) * 8),  // hit_off
-                          caller_qoff ? nullptr : reinterpret_cast<const u32*>(d_qoff),          // the host has its own copy
-                          ws[WS_QMETA].as<u32>() + nq,                                           // qdist, qflags, qnondna lie in this order
-                          ws[WS_QSEQ].as<u32>(), ws[WS_HITS].as<u32>(), ws[WS_OPS].as<u32>()};
-    const u64 offs[6] = {L.o_hit_off, L.o_qoff, L.o_meta, L.o_qseq, L.o_hits, L.o_ops};
-    const u64 words[6] = {(nq + 1) * 2, (nq + 1) * 2, 3 * (u64)nq, (total + 3) / 4, capn * (sizeof(dg_hit) / 4), capn * (u64)ops_per_hit};
-    u64 all = 0;
-    for (int k = 0; k < 6; ++k) {
-      pa.src[k] = srcs[k];
-      pa.dst_word[k] = offs[k] / 4;
-      pa.nwords[k] = words[k];
-      all += words[k];
-    }
-    if (!ops_per_hit) pa.src[5] = nullptr;
-    pa.nhits = (const u64*)(ws[WS_GRP].as<u8>() + (ngrp + 1) * 8) + nq;  // hit_off[nq]
-    pa.hit_words = (u32)(sizeof(dg_hit) / 4);
-    pa.op_words = ops_per_hit;
-    hipLaunchKernelGGL(k_pack_results, dim3(ceil_div(all, 256)), dim3(256), 0, st, pa, ws[WS_PACK].as<u32>());
-    DG_HIP(hipMemcpyAsync(pb->p, ws[WS_PACK].p, L.bytes, hipMemcpyDeviceToHost, st));
-    return DG_OK;
-  };
-  std::vector<u32> dump_cnt;
-  for (int attempt = 0;; ++attempt) {
-    if (attempt > 8) return fail(DG_ENOMEM, "buffer overflow persists (%llu leaves, %llu hits)", (unsigned long long)nleaf, (unsigned long long)nhits);
-    const u64 leaf_slots = (u64)NSHARD * shard_cap;
+}
 
-    // Distance 1, every string in 128 bits: k_search1s settles the select stage inside the search kernel (flat Sel region of
-    // NSHARD slices).  The generic kernels (k_search for N-containing / long queries, k_explicit, scan, pack, alive, rank) run
-    // when the previous batch of this handle had work for them; a batch that turns out to need them after all is repeated.
-    // DICEY_NO_FUSED_SELECT: the search without the select stage (k_search1p + the generic select kernels) — what batches with
-    // strings above 42 characters take anyway; the GPU tests run every distance-1 case both ways
-    const bool no_fuse = sw.no_fuse;
-    // r04: the same at edit distance 2 (k_search2p<true, .>: one workgroup per group or per query); DICEY_NO_FUSED_SELECT2 keeps the
-    // generic select kernels for that distance only
-    const bool fused = (b.fastK || (b.fast2K && !sw.no_fuse2)) && packed && !no_fuse;
-    const u32 flat_cap = fused ? flat_req : 0u;
-    const u64 flat_slots = (u64)NSHARD * flat_cap;
-    const bool generic_on = !fused || ix->generic_hint || nxs > 0 || force_generic;
-    bool jobs_on = false, walker_on = true, with_ctx_hits = false;
-    u32 direct_ctx = 0;
-    bool keys_on = false;  // this attempt's k_search1s wrote the kept strings' keys (FlatSel::key)
-    DG_TRY(ws[WS_LEAF].reserve(leaf_slots * sizeof(Leaf)));
-    DG_TRY(ws[WS_LEAFG].reserve((leaf_slots + 1) * (sizeof(Leaf) > sizeof(PLeaf) ? sizeof(Leaf) : sizeof(PLeaf))));
-    DG_TRY(ws[WS_SEL].reserve((flat_slots + leaf_slots + 1) * sizeof(Sel)));
-    Sel* const sel_all = ws[WS_SEL].as<Sel>();
-    Sel* const sel_gen = sel_all + flat_slots;  // the generic path's slots: grp_off based, behind the flat region
-    DG_TRY(ws[WS_SCR].reserve((leaf_slots + 1) * 5 + 64));
-    DG_TRY(ws[WS_SEEDS].reserve((hit_cap + 1) * sizeof(HitSeed)));
-    const u32 surv_cap = 0xFFFFFFFFu;  // (r02's survivor queue in HBM is gone with k_probe1 / k_finish1; the scan kernel's check keeps its argument)
-    // locate jobs: three lists of JOB_SHARDS regions each (hunt_locate.hpp); a region that fills up turns its strings away to the
-    // queueing lane, so the size is a matter of speed only
-    const u32 job_shard_cap = (u32)(std::min<u64>(leaf_slots, 1u << 20) / JOB_SHARDS * 3 / 2 + 32);
-    DG_TRY(ws[WS_JOBS].reserve(3 * (u64)JOB_SHARDS * job_shard_cap * sizeof(BigJob)));
-    DG_TRY(ws[WS_HITS].reserve((hit_cap + 1) * sizeof(dg_hit)));
-    if (stride && !sx && !group_counts) DG_TRY(ws[WS_ALN].reserve((hit_cap + 1) * 2 * (u64)stride));
-    if (!sx && !group_counts) DG_TRY(ws[WS_OPS].reserve((hit_cap + 1) * (u64)ops_per_hit * 4 + 64));
-    u32* d_chits = nullptr;
-    if (compact) {
-      DG_TRY(ws[WS_PACK].reserve(2 * (u64)nq * 4 + (hit_cap + 1) * (u64)chit_words * 4 + 64));
-      qhits = ws[WS_PACK].as<u32>();
-      b.qinfo = qhits + nq;
-      d_chits = qhits + 2 * nq;
+// What an attempt decides before its first launch (Attempt names the fields a stage sets later)
+static void decide_attempt(const dg_index* ix, const BatchPlan& pl, BatchBufs& bf, Attempt& at) {
+  const dg_switches& sw = ix->sw;
+  Batch& b = bf.b;
+  // Distance 1, every string in 128 bits: k_search1s settles the select stage inside the search kernel (flat Sel region of
+  // NSHARD slices).  The generic kernels (k_search for N-containing / long queries, k_explicit, scan, pack, alive, rank) run
+  // when the previous batch of this handle had work for them; a batch that turns out to need them after all is repeated.
+  // DICEY_NO_FUSED_SELECT: the search without the select stage (k_search1p + the generic select kernels) — what batches with
+  // strings above 42 characters take anyway; the GPU tests run every distance-1 case both ways
+  // r04: the same at edit distance 2 (k_search2p<true, .>: one workgroup per group or per query); DICEY_NO_FUSED_SELECT2 keeps the
+  // generic select kernels for that distance only
+  at.fused = (b.fastK || (b.fast2K && !sw.no_fuse2)) && pl.packed && !sw.no_fuse;
+  at.flat_cap = at.fused ? at.flat_req : 0u;
+  at.generic_on = !at.fused || ix->generic_hint || bf.nxs > 0 || at.force_generic;
+  // edit distance 2: the walker (k_search) only serves the groups k_search2p does not take (N in the query, above 30 nt); it is
+  // launched when the previous batch of the handle had such groups — 0.17 ms of the 13 ms step on batches that have none — and
+  // a batch that has some after all is repeated with it, like the generic kernels at distance 1
+  at.walker_on = !(b.fast2K && !ix->generic_hint && !at.force_generic && bf.nxs == 0);
+  // distance 2: the LONG2 body of k_search2p takes queries whose shortest string still asks the long filter; the handle falls back to
+  // the r04 body while its batches hold shorter ones (short2_sticky), and a batch that turns out to hold some is repeated with it
+  at.long2 = b.fast2K && ix->view.kf2.nr && ix->view.kf2.k <= 18 /* word offsets inside a copy stay below 2^32 */ && !ix->short2_sticky && !at.force_short2 && !sw.no_long2;
+  b.fast2_minlen = at.long2 ? ix->view.kf2.k + (pl.indel ? 2u : 0u) : 0u;
+  // the whole batch on the flat distance-1 path: k_search1s settles the `take` values of its own queries (TAKE form);
+  // DICEY_NO_PREP_FUSION keeps k_take a launch of its own (the GPU suite runs both)
+  at.prep_in = at.fused && b.fastK && !at.generic_on && !pl.group_counts && !sw.no_prep_fusion;
+  at.flat_form = b.fastK ? (at.fused ? (at.prep_in ? 3u : 2u) : 1u) : b.fast2K ? (at.fused ? 5u : 4u) + (at.long2 ? 2u : 0u) : 0u;
+  // hits of the job kernels leave with their context characters (FmView::sax) when the kernel that reads the seeds is
+  // k_verify_memo — the only reader that knows the encoding (HitSeed::len, devfm.hpp)
+  at.with_ctx_hits = pl.hunt && pl.band_verify && ix->view.sax;
+  at.keys_on = at.jobs_on = false;
+  at.direct_ctx = 0;
+}
+
+// (r02's survivor queue in HBM is gone with k_probe1 / k_finish1; the scan kernel's check keeps its argument)
+static constexpr u32 SURV_CAP = 0xFFFFFFFFu;
+
+// The workspaces whose size follows the attempt's capacities
+static int reserve_attempt(dg_index* ix, const BatchPlan& pl, const Attempt& at, BatchBufs& bf) {
+  auto& ws = ix->ws;
+  const u64 leaf_slots = bf.leaf_slots = (u64)NSHARD * at.shard_cap;
+  const u64 flat_slots = bf.flat_slots = (u64)NSHARD * at.flat_cap;
+  const u64 hit_cap = at.hit_cap;
+  DG_TRY(ws[WS_LEAF].reserve(leaf_slots * sizeof(Leaf)));
+  DG_TRY(ws[WS_LEAFG].reserve((leaf_slots + 1) * (sizeof(Leaf) > sizeof(PLeaf) ? sizeof(Leaf) : sizeof(PLeaf))));
+  DG_TRY(ws[WS_SEL].reserve((flat_slots + leaf_slots + 1) * sizeof(Sel)));
+  bf.sel_all = ws[WS_SEL].as<Sel>();
+  bf.sel_gen = bf.sel_all + flat_slots;
+  DG_TRY(ws[WS_SCR].reserve((leaf_slots + 1) * 5 + 64));
+  DG_TRY(ws[WS_SEEDS].reserve((hit_cap + 1) * sizeof(HitSeed)));
+  // locate jobs: three lists of JOB_SHARDS regions each (hunt_locate.hpp); a region that fills up turns its strings away to the
+  // queueing lane, so the size is a matter of speed only
+  bf.job_shard_cap = (u32)(std::min<u64>(leaf_slots, 1u << 20) / JOB_SHARDS * 3 / 2 + 32);
+  DG_TRY(ws[WS_JOBS].reserve(3 * (u64)JOB_SHARDS * bf.job_shard_cap * sizeof(BigJob)));
+  DG_TRY(ws[WS_HITS].reserve((hit_cap + 1) * sizeof(dg_hit)));
+  if (pl.stride && pl.hunt) DG_TRY(ws[WS_ALN].reserve((hit_cap + 1) * 2 * (u64)pl.stride));
+  if (pl.hunt) DG_TRY(ws[WS_OPS].reserve((hit_cap + 1) * (u64)pl.ops_per_hit * 4 + 64));
+  bf.d_chits = nullptr;
+  if (pl.compact) {
+    DG_TRY(ws[WS_PACK].reserve(2 * (u64)pl.nq * 4 + (hit_cap + 1) * (u64)pl.chit_words * 4 + 64));
+    bf.qhits = ws[WS_PACK].as<u32>();
+    bf.b.qinfo = bf.qhits + pl.nq;
+    bf.d_chits = bf.qhits + 2 * pl.nq;
+  }
+  return DG_OK;
+}
+
+static int launch_prepare(dg_index* ix, const BatchPlan& pl, const Attempt& at, BatchBufs& bf) {
+  hipStream_t st = ix->stream;
+  // the per-character arrays (fw / rv codes, normalised ASCII) are read by the generic kernels, the full-matrix verify kernels and
+  // the classic result fetch only: 60 byte stores per query that the flat path with compact results does without
+  const u32 write_bytes = (at.prep_in && pl.band_verify && (pl.compact || !pl.fetch)) ? 0u : 1u;
+  hipLaunchKernelGGL(k_prepare, dim3(ceil_div(pl.nq, TB)), dim3(TB), 0, st, bf.b, bf.grp_cnt, bf.nsel, bf.selbase, (u32*)&bf.ctr->pad_[CW_N_GENERIC],
+                     write_bytes);
+  DG_HIP(hipEventRecord(ix->ev[EV_PREPARED], st));
+  return DG_OK;
+}
+
+static FlatSel flat_sel(const Attempt& at, const BatchBufs& bf) {
+  FlatSel fs;
+  fs.sel = bf.sel_all;
+  fs.cap = at.flat_cap;
+  fs.selbase = bf.selbase;
+  fs.nsel = bf.nsel;
+  fs.key = nullptr;
+  return fs;
+}
+
+// distance 1: the flat kernel takes every query that qualifies, k_search (one lane per strand) the rest
+static int launch_flat1(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBufs& bf, const SearchOut& so) {
+  hipStream_t st = ix->stream;
+  const dg_switches& sw = ix->sw;
+  const Batch& b = bf.b;
+  const u32 ipg = std::min(pl.maxlen, 31u), magic = (65536u + ipg - 1) / ipg;  // longer queries stay with k_search
+  if (at.fused) {
+    const u32 gpw = at.prep_in ? (std::min(16u, 256u / ipg) & ~1u) : std::min(16u, 256u / ipg);  // TAKE: both strands of a query in one workgroup
+    FlatSel fs = flat_sel(at, bf);
+    // r06: strings with one occurrence leave with their characters when the locate / verify stages of this batch can use them
+    // (direct_ctx in launch_locate: the records are resident, distance <= 1, banded verify)
+    if (pl.hunt && pl.band_verify && ix->view.sax && pl.indel && pl.dmax_eff <= 1 && !sw.no_direct_ctx) {
+      DG_TRY(ix->ws[WS_SELKEY].reserve((bf.flat_slots + 1) * 8));
+      fs.key = ix->ws[WS_SELKEY].as<u64>();
+      at.keys_on = true;
     }
-    // counters: left zeroed by the previous batch's last kernel (batch_finish) unless they moved or that batch did not finish;
-    // group counters: cleared by k_prepare
-    if (ix->ctr_clean != (const void*)ctr || ix->ctr_clean_gen != ws[WS_GRP].gen) DG_HIP(hipMemsetAsync(zero_from, 0, zero_bytes, st));
-    ix->ctr_clean = nullptr;  // dirty until this attempt's last kernel has run
-    DG_HIP(hipEventRecord(ix->ev[0], st));
-    // the whole batch on the flat distance-1 path: k_search1s settles the `take` values of its own queries (TAKE form);
-    // DICEY_NO_PREP_FUSION keeps k_take a launch of its own (the GPU suite runs both)
-    // distance 2: the LONG2 body of k_search2p takes queries whose shortest string still asks the long filter; the handle falls back to
-    // the r04 body while its batches hold shorter ones (short2_sticky), and a batch that turns out to hold some is repeated with it
-    const bool long2 = b.fast2K && ix->view.kf2.nr && ix->view.kf2.k <= 18 /* word offsets inside a copy stay below 2^32 */ && !ix->short2_sticky && !force_short2 && !sw.no_long2;
-    b.fast2_minlen = long2 ? ix->view.kf2.k + (indel ? 2u : 0u) : 0u;
-    const bool prep_in = fused && b.fastK && !generic_on && !group_counts && !sw.no_prep_fusion;
-    flat_form = b.fastK ? (fused ? (prep_in ? 3u : 2u) : 1u) : b.fast2K ? (fused ? 5u : 4u) + (long2 ? 2u : 0u) : 0u;
-    // the per-character arrays (fw / rv codes, normalised ASCII) are read by the generic kernels, the full-matrix verify kernels and
-    // the classic result fetch only: 60 byte stores per query that the flat path with compact results does without
-    const u32 write_bytes = (prep_in && band_verify && (compact || !fetch)) ? 0u : 1u;
-    hipLaunchKernelGGL(k_prepare, dim3(ceil_div(nq, TB)), dim3(TB), 0, st, b, grp_cnt, nsel, selbase, (u32*)&ctr->pad_[6], write_bytes);
-    DG_HIP(hipEventRecord(ix->ev[1], st));
-    {
-      SearchOut so;
-      WalkList kl{nullptr, nullptr, 0u};  // the strands of k_nkeep (k_walk_list)
-      so.leaves = ws[WS_LEAF].as<Leaf>();
-      so.shard_cap = shard_cap;
-      so.ctr = ctr;
-      so.grp_cnt = grp_cnt;
-      if (b.fastK) {  // distance 1: the flat kernel takes every query that qualifies, k_search (one lane per strand) the rest
-        const u32 ipg = std::min(maxlen, 31u), magic = (65536u + ipg - 1) / ipg;  // longer queries stay with k_search
-        if (fused) {
-          const u32 gpw = prep_in ? (std::min(16u, 256u / ipg) & ~1u) : std::min(16u, 256u / ipg);  // TAKE: both strands of a query in one workgroup
-          FlatSel fs;
-          fs.sel = sel_all;
-          fs.cap = flat_cap;
-          fs.selbase = selbase;
-          fs.nsel = nsel;
-          // r06: strings with one occurrence leave with their characters when the locate / verify stages of this batch can use them
-          // (direct_ctx below: the records are resident, distance <= 1, banded verify)
-          fs.key = nullptr;
-          if (!sx && !group_counts && band_verify && ix->view.sax && indel && dmax_eff <= 1 && !sw.no_direct_ctx) {
-            DG_TRY(ws[WS_SELKEY].reserve((flat_slots + 1) * 8));
-            fs.key = ws[WS_SELKEY].as<u64>();
-            keys_on = true;
-          }
-          const dim3 g1(ceil_div(ngrp, gpw)), b1(256);
-          // LDS list of a workgroup: 256 entries unless the previous batch of this handle averaged more than 48 occurring strings
-          // per workgroup (repeat-bearing genomes), then 512; a workgroup whose strings do not fit hands its groups to the generic
-          // path.  tests: DICEY_FUSED_LCAP lowers the capacity so that ordinary batches exercise that hand-over
-          const u32 lcap_env = sw.fused_lcap ? std::max<u32>(1u, std::min<u32>(FUSED_LCAP, sw.fused_lcap)) : 0u;
-          const u32 lcap = lcap_env ? lcap_env : (ix->fused_leaves_hint > 48ull * g1.x ? FUSED_LCAP : FUSED_LCAP / 2);
-          const u32 lds1 = fused_lds_bytes(lcap);
-          const u32 leave1 = 1u | (sw.exp_bits << 1);  // bit 0: idle wavefronts end behind the probe phase (r04 A/B on one box: 0.2188 ms with, 0.2194 without — harmless, kept)
-          PrepOut po;
-          po.qhits = qhits;
-          if (prep_in) {
-            if (indel) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search1s<true, true>), g1, b1, lds1, st, ix->view, b, so, fs, ipg, magic, gpw, lcap, leave1, po);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search1s<false, true>), g1, b1, lds1, st, ix->view, b, so, fs, ipg, magic, gpw, lcap, leave1, po);
-          } else {
-            if (indel) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search1s<true, false>), g1, b1, lds1, st, ix->view, b, so, fs, ipg, magic, gpw, lcap, leave1, po);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search1s<false, false>), g1, b1, lds1, st, ix->view, b, so, fs, ipg, magic, gpw, lcap, leave1, po);
-          }
-        } else {
-          const dim3 g1(ceil_div(ngrp * ipg, TB)), b1(TB);
-          if (indel) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search1p<true>), g1, b1, 0, st, ix->view, b, so, ipg, magic);
-          else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search1p<false>), g1, b1, 0, st, ix->view, b, so, ipg, magic);
-        }
-        DG_HIP(hipEventRecord(ix->ev[8], st));
-      }
-      if (b.fast2K) {  // edit distance 2: one workgroup per (query, strand) for every query that qualifies
-        // filtered leaves only where the packed select path (k_group_pack) hands the filter word on
-        const u32 filt_ok = (u32)(packed && !sw.no_pre5_d2);
-        FlatSel fs;
-        fs.sel = sel_all;
-        fs.cap = flat_cap;
-        fs.selbase = selbase;
-        fs.nsel = nsel;
-        fs.key = nullptr;
-        // (tests: DICEY_FUSED_LCAP lowers the list's capacity so that ordinary groups exercise the hand-over to the generic select kernels)
-        const u32 lcap2 = sw.fused_lcap ? std::max<u32>(1u, std::min<u32>(FUSED2_LCAP, sw.fused_lcap)) : FUSED2_LCAP;
-        const u32 ham2 = (indel ? 0u : 1u) | (sw.exp_bits << 8);  // (DICEY_EXP: k_search2p's measurement switches)
-        if (fused && long2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search2p<true, true>), dim3((u32)ngrp), dim3(TB), 0, st, ix->view, b, so, filt_ok, fs, lcap2, ham2);
-        else if (fused) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search2p<true, false>), dim3((u32)ngrp), dim3(TB), 0, st, ix->view, b, so, filt_ok, fs, lcap2, ham2);
-        else if (long2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search2p<false, true>), dim3((u32)ngrp), dim3(TB), 0, st, ix->view, b, so, filt_ok, fs, lcap2, ham2);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search2p<false, false>), dim3((u32)ngrp), dim3(TB), 0, st, ix->view, b, so, filt_ok, fs, lcap2, ham2);
-        DG_HIP(hipEventRecord(ix->ev[8], st));
-      }
-      // edit distance 2: the walker (k_search) only serves the groups k_search2p does not take (N in the query, above 30 nt); it is
-      // launched when the previous batch of the handle had such groups — 0.17 ms of the 13 ms step on batches that have none — and
-      // a batch that has some after all is repeated with it, like the generic kernels at distance 1
-      walker_on = !(b.fast2K && !ix->generic_hint && !force_generic && nxs == 0);
-      if (generic_on && walker_on) {
-      // root-level work split (see k_search): only with the table and with at least one edit to place
-      // (r05: also beside the flat distance-1 kernel — the walker is only launched when a batch has groups for it, and those are the
-      // queries with N that the split turns from one 1 500-read chain per strand into lanes of a handful of reads)
-      // — while the handle's batches hold such strands (nwin_sticky): 29 M lanes that leave at once cost a repeats-genome step 0.15 ms
-      const u32 items = (ix->view.K && dmax_eff >= 1 && (!b.fastK || ix->nwin_sticky)) ? ix->view.K * (indel ? 9u : 4u) + 1u : 1u;
-      // beside a flat kernel the walker serves a few strands of the batch: with the root split its lanes cover a LIST of them
-      // (k_walk_list; room for what the previous batch listed plus a quarter — a list that overflows repeats the batch)
-      WalkList wl{nullptr, nullptr, 0u};
-      u64 wgroups = ngrp;
-      // (r06 fix: also for a batch WITHOUT a flat kernel — queries shorter than the table order — when k_prepare may mark strands for
-      //  k_nkeep (b.nrun_min): they are found through this list only; the list then simply holds every group, no hint involved.
-      //  tools/fuzz_hunt.py in the full-size layout found a 12-mer ending in N that lost its two exact hits in Hamming mode)
-      const bool flat_on = b.fastK || b.fast2K;
-      if ((flat_on || b.nrun_min) && ngrp < 0x7FFFFFFFull) {
-        walk_cap = std::max<u64>(walk_cap, flat_on ? std::min<u64>(ngrp, (u64)ix->walk_hint + ix->walk_hint / 4 + 4096) : ngrp);
-        DG_TRY(ws[WS_WALK].reserve(2 * (walk_cap + 1) * 4));
-        wl.gid = ws[WS_WALK].as<u32>();
-        wl.count = &ctr->pad_[10];
-        wl.cap = (u32)walk_cap;
-        wgroups = walk_cap;
-        kl.gid = ws[WS_WALK].as<u32>() + walk_cap + 1;  // the strands of k_nkeep, behind the walker's groups
-        kl.count = &ctr->pad_[11];
-        kl.cap = (u32)walk_cap;
-        hipLaunchKernelGGL(k_walk_list, dim3(ceil_div(ngrp, TB)), dim3(TB), 0, st, b, ws[WS_WALK].as<u32>(), &ctr->pad_[10],
-                           ws[WS_WALK].as<u32>() + walk_cap + 1, &ctr->pad_[11], wl.cap, ctr);
-      }
-      const dim3 grid(ceil_div(wgroups * items, TB)), block(TB);
-#define DG_LAUNCH_SEARCH(IND, DD) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search<IND, DD>), grid, block, 0, st, ix->view, b, so, items, wl)
-      if (indel) {
-        if (dmax_eff == 0) DG_LAUNCH_SEARCH(true, 0);
-        else if (dmax_eff == 1) DG_LAUNCH_SEARCH(true, 1);
-        else if (dmax_eff == 2) DG_LAUNCH_SEARCH(true, 2);
-        else DG_LAUNCH_SEARCH(true, 4);
-      } else {
-        if (dmax_eff == 0) DG_LAUNCH_SEARCH(false, 0);
-        else if (dmax_eff == 1) DG_LAUNCH_SEARCH(false, 1);
-        else if (dmax_eff == 2) DG_LAUNCH_SEARCH(false, 2);
-        else DG_LAUNCH_SEARCH(false, 4);
-      }
-#undef DG_LAUNCH_SEARCH
-      if (nxs) hipLaunchKernelGGL(k_explicit, dim3(ceil_div(nxs, TB)), dim3(TB), 0, st, ix->view, b, so);
-      }
-      // strands whose N's can only be substituted or deleted (k_prepare, bit 12 of GidInfo::d_win): a lane per resolved string
-      if (generic_on && b.nrun_min) {
-        const u32 per = indel ? (dmax_eff == 1 ? 5u : 25u) : (dmax_eff == 1 ? 4u : 16u);
-        if (indel) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nres<true>), dim3(ceil_div(ngrp * per, TB)), dim3(TB), 0, st, ix->view, b, so, per);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nres<false>), dim3(ceil_div(ngrp * per, TB)), dim3(TB), 0, st, ix->view, b, so, per);
-        // ... and the strings of the listed bit-13 strands that keep their N: a lane per candidate edit
-        if (kl.gid) {
-          const u32 kper = 1u + (indel ? 9u : 3u) * std::min(maxlen, 32u);
-          if (indel) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nkeep<true>), dim3(ceil_div((u64)kl.cap * kper, TB)), dim3(TB), 0, st, ix->view, b, so, kl, kper);
-          else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nkeep<false>), dim3(ceil_div((u64)kl.cap * kper, TB)), dim3(TB), 0, st, ix->view, b, so, kl, kper);
-        }
-      }
-    }
-    if (phase_events) DG_HIP(hipEventRecord(ix->ev[2], st));
-    // (r03 tried single-launch scans chained by decoupled look-back, and k_take fused with its scan: 17 us against 2 x 4.3 us, and
-    //  47 us against 7 + 9 us — descriptor polling with device-scope acquire / release is slow across the XCDs' L2s.  What stays of
-    //  that round: the first scan kernel also checks the search kernels' buffers, which was a launch of its own.)
-    if (generic_on) DG_TRY(device_scan(st, grp_cnt, ngrp, grp_off, scan_buf, ctr, shard_cap, surv_cap));
-    if (phase_events) DG_HIP(hipEventRecord(ix->ev[3], st));
-    if (packed) {
-      if (generic_on) {
+    const dim3 g1(ceil_div(pl.ngrp, gpw)), b1(256);
+    // LDS list of a workgroup: 256 entries unless the previous batch of this handle averaged more than 48 occurring strings
+    // per workgroup (repeat-bearing genomes), then 512; a workgroup whose strings do not fit hands its groups to the generic
+    // path.  tests: DICEY_FUSED_LCAP lowers the capacity so that ordinary batches exercise that hand-over
+    const u32 lcap_env = sw.fused_lcap ? std::max<u32>(1u, std::min<u32>(FUSED_LCAP, sw.fused_lcap)) : 0u;
+    const u32 lcap = lcap_env ? lcap_env : (ix->fused_leaves_hint > 48ull * g1.x ? FUSED_LCAP : FUSED_LCAP / 2);
+    const u32 lds1 = fused_lds_bytes(lcap);
+    const u32 leave1 = 1u | (sw.exp_bits << 1);  // bit 0: idle wavefronts end behind the probe phase (r04 A/B on one box: 0.2188 ms with, 0.2194 without — harmless, kept)
+    PrepOut po;
+    po.qhits = bf.qhits;
+    with_flag(pl.indel, [&](auto I) {
+      with_flag(at.prep_in, [&](auto T) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search1s<decltype(I)::value, decltype(T)::value>), g1, b1, lds1, st, ix->view, b, so, fs, ipg, magic, gpw, lcap, leave1, po);
+      });
+    });
+  } else {
+    const dim3 g1(ceil_div(pl.ngrp * ipg, TB)), b1(TB);
+    with_flag(pl.indel, [&](auto I) { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search1p<decltype(I)::value>), g1, b1, 0, st, ix->view, b, so, ipg, magic); });
+  }
+  DG_HIP(hipEventRecord(ix->ev[EV_FLAT_END], st));
+  return DG_OK;
+}
+
+// edit distance 2: one workgroup per (query, strand) for every query that qualifies
+static int launch_flat2(dg_index* ix, const BatchPlan& pl, const Attempt& at, BatchBufs& bf, const SearchOut& so) {
+  hipStream_t st = ix->stream;
+  const dg_switches& sw = ix->sw;
+  const Batch& b = bf.b;
+  // filtered leaves only where the packed select path (k_group_pack) hands the filter word on
+  const u32 filt_ok = (u32)(pl.packed && !sw.no_pre5_d2);
+  const FlatSel fs = flat_sel(at, bf);
+  // (tests: DICEY_FUSED_LCAP lowers the list's capacity so that ordinary groups exercise the hand-over to the generic select kernels)
+  const u32 lcap2 = sw.fused_lcap ? std::max<u32>(1u, std::min<u32>(FUSED2_LCAP, sw.fused_lcap)) : FUSED2_LCAP;
+  const u32 ham2 = (pl.indel ? 0u : 1u) | (sw.exp_bits << 8);  // (DICEY_EXP: k_search2p's measurement switches)
+  with_flag(at.fused, [&](auto S) {
+    with_flag(at.long2, [&](auto L) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search2p<decltype(S)::value, decltype(L)::value>), dim3((u32)pl.ngrp), dim3(TB), 0, st, ix->view, b, so, filt_ok, fs, lcap2, ham2);
+    });
+  });
+  DG_HIP(hipEventRecord(ix->ev[EV_FLAT_END], st));
+  return DG_OK;
+}
+
+// the walker (k_search) over every group or over the groups k_walk_list lists, and the explicit patterns
+static int launch_walker(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBufs& bf, const SearchOut& so) {
+  hipStream_t st = ix->stream;
+  auto& ws = ix->ws;
+  const Batch& b = bf.b;
+  Counters* ctr = bf.ctr;
+  const u64 ngrp = pl.ngrp;
+  // root-level work split (see k_search): only with the table and with at least one edit to place
+  // (r05: also beside the flat distance-1 kernel — the walker is only launched when a batch has groups for it, and those are the
+  // queries with N that the split turns from one 1 500-read chain per strand into lanes of a handful of reads)
+  // — while the handle's batches hold such strands (nwin_sticky): 29 M lanes that leave at once cost a repeats-genome step 0.15 ms
+  const u32 items = (ix->view.K && pl.dmax_eff >= 1 && (!b.fastK || ix->nwin_sticky)) ? ix->view.K * (pl.indel ? 9u : 4u) + 1u : 1u;
+  // beside a flat kernel the walker serves a few strands of the batch: with the root split its lanes cover a LIST of them
+  // (k_walk_list; room for what the previous batch listed plus a quarter — a list that overflows repeats the batch)
+  WalkList wl{nullptr, nullptr, 0u};
+  u64 wgroups = ngrp;
+  // (r06 fix: also for a batch WITHOUT a flat kernel — queries shorter than the table order — when k_prepare may mark strands for
+  //  k_nkeep (b.nrun_min): they are found through this list only; the list then simply holds every group, no hint involved.
+  //  tools/fuzz_hunt.py in the full-size layout found a 12-mer ending in N that lost its two exact hits in Hamming mode)
+  const bool flat_on = b.fastK || b.fast2K;
+  if ((flat_on || b.nrun_min) && ngrp < 0x7FFFFFFFull) {
+    const u64 walk_cap = at.walk_cap = std::max<u64>(at.walk_cap, flat_on ? std::min<u64>(ngrp, (u64)ix->walk_hint + ix->walk_hint / 4 + 4096) : ngrp);
+    DG_TRY(ws[WS_WALK].reserve(2 * (walk_cap + 1) * 4));
+    wl.gid = ws[WS_WALK].as<u32>();
+    wl.count = &ctr->pad_[CW_N_WALK];
+    wl.cap = (u32)walk_cap;
+    wgroups = walk_cap;
+    bf.kl.gid = ws[WS_WALK].as<u32>() + walk_cap + 1;  // the strands of k_nkeep, behind the walker's groups
+    bf.kl.count = &ctr->pad_[CW_N_KEEP];
+    bf.kl.cap = (u32)walk_cap;
+    hipLaunchKernelGGL(k_walk_list, dim3(ceil_div(ngrp, TB)), dim3(TB), 0, st, b, ws[WS_WALK].as<u32>(), &ctr->pad_[CW_N_WALK],
+                       ws[WS_WALK].as<u32>() + walk_cap + 1, &ctr->pad_[CW_N_KEEP], wl.cap, ctr);
+  }
+  const dim3 grid(ceil_div(wgroups * items, TB)), block(TB);
+  with_flag(pl.indel, [&](auto I) {
+    with_value<0, 1, 2, 4>(pl.dmax_eff, [&](auto D) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search<decltype(I)::value, (int)decltype(D)::value>), grid, block, 0, st, ix->view, b, so, items, wl);
+    });
+  });
+  if (bf.nxs) hipLaunchKernelGGL(k_explicit, dim3(ceil_div(bf.nxs, TB)), dim3(TB), 0, st, ix->view, b, so);
+  return DG_OK;
+}
+
+// strands whose N's can only be substituted or deleted (k_prepare, bit 12 of GidInfo::d_win): a lane per resolved string
+static void launch_nres(dg_index* ix, const BatchPlan& pl, const BatchBufs& bf, const SearchOut& so) {
+  hipStream_t st = ix->stream;
+  const Batch& b = bf.b;
+  const WalkList& kl = bf.kl;
+  const u32 per = pl.indel ? (pl.dmax_eff == 1 ? 5u : 25u) : (pl.dmax_eff == 1 ? 4u : 16u);
+  with_flag(pl.indel, [&](auto I) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nres<decltype(I)::value>), dim3(ceil_div(pl.ngrp * per, TB)), dim3(TB), 0, st, ix->view, b, so, per);
+  });
+  // ... and the strings of the listed bit-13 strands that keep their N: a lane per candidate edit
+  if (kl.gid) {
+    const u32 kper = 1u + (pl.indel ? 9u : 3u) * std::min(pl.maxlen, 32u);
+    with_flag(pl.indel, [&](auto I) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nkeep<decltype(I)::value>), dim3(ceil_div((u64)kl.cap * kper, TB)), dim3(TB), 0, st, ix->view, b, so, kl, kper);
+    });
+  }
+}
+
+// Search stage: the flat kernel of the batch's distance, then what the generic path adds (walker, explicit patterns, N strands)
+static int launch_search(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBufs& bf) {
+  SearchOut so;
+  so.leaves = ix->ws[WS_LEAF].as<Leaf>();
+  so.shard_cap = at.shard_cap;
+  so.ctr = bf.ctr;
+  so.grp_cnt = bf.grp_cnt;
+  bf.kl = WalkList{nullptr, nullptr, 0u};
+  if (bf.b.fastK) DG_TRY(launch_flat1(ix, pl, at, bf, so));
+  if (bf.b.fast2K) DG_TRY(launch_flat2(ix, pl, at, bf, so));
+  if (at.generic_on && at.walker_on) DG_TRY(launch_walker(ix, pl, at, bf, so));
+  if (at.generic_on && bf.b.nrun_min) launch_nres(ix, pl, bf, so);
+  if (pl.phase_events) DG_HIP(hipEventRecord(ix->ev[EV_SEARCHED], ix->stream));
+  return DG_OK;
+}
+
+// Select stage: group offsets, then duplicates out / substring-minimal strings / std::set order per group, then `take` per query
+static int launch_select(dg_index* ix, const BatchPlan& pl, const Attempt& at, BatchBufs& bf) {
+  hipStream_t st = ix->stream;
+  auto& ws = ix->ws;
+  const Batch& b = bf.b;
+  Counters* ctr = bf.ctr;
+  u64* grp_off = bf.grp_off;
+  u32* nsel = bf.nsel;
+  const u64 ngrp = pl.ngrp, leaf_slots = bf.leaf_slots;
+  // (r03 tried single-launch scans chained by decoupled look-back, and k_take fused with its scan: 17 us against 2 x 4.3 us, and
+  //  47 us against 7 + 9 us — descriptor polling with device-scope acquire / release is slow across the XCDs' L2s.  What stays of
+  //  that round: the first scan kernel also checks the search kernels' buffers, which was a launch of its own.)
+  if (at.generic_on) DG_TRY(device_scan(st, bf.grp_cnt, ngrp, grp_off, bf.scan_buf, ctr, at.shard_cap, SURV_CAP));
+  if (pl.phase_events) DG_HIP(hipEventRecord(ix->ev[EV_GROUPS_SCANNED], st));
+  if (pl.packed) {
+    if (at.generic_on) {
       u8* alive = ws[WS_SCR].as<u8>();
       // the leaves' filter words sit behind the packed leaves: the buffer is sized for 36-byte Leaf records, PLeaf takes 32
       static_assert(sizeof(Leaf) >= sizeof(PLeaf) + sizeof(u32), "room for the filter words");
       u32* filt = (u32*)((u8*)ws[WS_LEAFG].p + (leaf_slots + 1) * sizeof(PLeaf));
-      hipLaunchKernelGGL(k_group_pack, dim3(ceil_div(leaf_slots, TB)), dim3(TB), 0, st, b, ws[WS_LEAF].as<Leaf>(), shard_cap, ctr,
-                         grp_off, ws[WS_LEAFG].as<PLeaf>(), filt);
+      hipLaunchKernelGGL(k_group_pack, dim3(ceil_div(leaf_slots, TB)), dim3(TB), 0, st, b, ws[WS_LEAF].as<Leaf>(), at.shard_cap, ctr, grp_off,
+                         ws[WS_LEAFG].as<PLeaf>(), filt);
       // distance >= 2: groups of up to SELCAP strings are sorted by a workgroup each, the lane-per-leaf kernels keep the rest
-      const u32 above = (dmax_eff >= 2 && ngrp < 0x7FFFFFFFull) ? SELCAP : 0u;
+      const u32 above = (pl.dmax_eff >= 2 && ngrp < 0x7FFFFFFFull) ? SELCAP : 0u;
       if (above)
         // (one wavefront per group was tried: 1.95 -> 2.5 ms, the second wavefront's share of the window searches is worth more than the barriers)
-        hipLaunchKernelGGL(k_group_select, dim3((u32)ngrp), dim3(128), 0, st, ws[WS_LEAFG].as<PLeaf>(), (const u32*)filt, grp_off, (u32)indel,
-                           sel_gen, nsel, ctr);
-      hipLaunchKernelGGL(k_leaf_alive, dim3(ceil_div(leaf_slots, TB)), dim3(TB), 0, st, ws[WS_LEAFG].as<PLeaf>(), grp_off, ngrp,
-                         (u32)indel, alive, ctr, above);
+        hipLaunchKernelGGL(k_group_select, dim3((u32)ngrp), dim3(128), 0, st, ws[WS_LEAFG].as<PLeaf>(), (const u32*)filt, grp_off, (u32)pl.indel,
+                           bf.sel_gen, nsel, ctr);
+      hipLaunchKernelGGL(k_leaf_alive, dim3(ceil_div(leaf_slots, TB)), dim3(TB), 0, st, ws[WS_LEAFG].as<PLeaf>(), grp_off, ngrp, (u32)pl.indel, alive,
+                         ctr, above);
       hipLaunchKernelGGL(k_leaf_rank, dim3(ceil_div(leaf_slots, TB)), dim3(TB), 0, st, ws[WS_LEAFG].as<PLeaf>(), (const u32*)filt, grp_off, ngrp,
-                         (const u8*)alive, sel_gen, nsel, ctr, above);
-      }
-      if (!prep_in)
-        hipLaunchKernelGGL(k_take, dim3(ceil_div(nq * 16, 256)), dim3(256), 0, st, b, (const u64*)grp_off, (const u32*)selbase, flat_slots, (const u32*)nsel, sel_all,
-                           qhits, ctr);
-    } else {
-      hipLaunchKernelGGL(k_group, dim3(ceil_div(leaf_slots, TB)), dim3(TB), 0, st, ws[WS_LEAF].as<Leaf>(), shard_cap, ctr, grp_off,
-                         ws[WS_LEAFG].as<Leaf>());
-      u32* scr_rank = ws[WS_SCR].as<u32>();
-      u8* scr_keep = (u8*)(scr_rank + leaf_slots + 1);
-      hipLaunchKernelGGL(k_select, dim3(ceil_div(nq, 64)), dim3(64), 0, st, b, ws[WS_LEAFG].as<Leaf>(), grp_off, sel_gen,
-                         nsel, qhits, scr_keep, scr_rank, ctr);
+                         (const u8*)alive, bf.sel_gen, nsel, ctr, above);
     }
-    if (phase_events) DG_HIP(hipEventRecord(ix->ev[4], st));
-    if (group_counts) {
-      DG_TRY(ws[WS_HITS].reserve(ngrp * 8 + 64));
-      hipLaunchKernelGGL(k_group_count, dim3(ceil_div(ngrp, TB)), dim3(TB), 0, st, (const u64*)grp_off, (const u32*)selbase, flat_slots,
-                         (const u32*)nsel, (const Sel*)sel_all, ngrp, ws[WS_HITS].as<u64>(), ctr);
-      DG_HIP(hipMemsetAsync(hit_off + nq, 0, 8, st));  // no hits in this mode
-      for (int e = 5; e <= 7; ++e)
-        if (phase_events || e == 7) DG_HIP(hipEventRecord(ix->ev[e], st));
-    } else {
-    DG_TRY(device_scan(st, qhits, nq, hit_off, scan_buf));
-    if (phase_events) DG_HIP(hipEventRecord(ix->ev[5], st));
-    {
-      // strings with many occurrences go to three job lists: up to 256 occurrences for a wavefront each, more for a workgroup each
-      // (those that fit the small buffer of k_locate_topk whole, and the rest)
-      jobs_on = ix->jobs_hint || force_jobs || p->max_locations > TOPK_KMAX;
-      // repeat-rich strings: up to TOPK_KMAX positions through the block minima, more (hunt -m above 1 024) by radix passes
-      const bool topk = ix->view.nlev > 1;
-      // A batch with thousands of repeat-rich strings (the previous batch of this handle tells): intervals up to 4 608 entries go
-      // to the small-buffer form of k_locate_topk.  (r03 also ran the three job kernels side by side on helper streams: each
-      // slowed down by what the others took — 114 / 220 / 228 us alone, 220 / 494 / 268 us together — and the stage gained
-      // 0.08 of 0.91 ms; not worth two more streams per handle.)
-      const bool rich = topk && ix->jobs_big_hint >= 2048;
-      LocJobs lj;
-      for (int l = 0; l < 3; ++l) lj.list[l] = ws[WS_JOBS].as<BigJob>() + (u64)l * JOB_SHARDS * job_shard_cap;
-      lj.shard_cap = job_shard_cap;
-      lj.cnt = ctr->job_cnt;
-      lj.mid_max = rich ? 8 * TOPK_KCAP_MID : 0u;
-      // hits of the job kernels leave with their context characters (FmView::sax) when the kernel that reads the seeds is
-      // k_verify_memo — the only reader that knows the encoding (HitSeed::len, devfm.hpp)
-      const u32 with_ctx = (!sx && !group_counts && band_verify && ix->view.sax) ? 1u : 0u;
-      with_ctx_hits = with_ctx != 0;
-      // r06: the same for a string with ONE occurrence that k_locate serves itself, when the search kernel knew the character in front
-      // of it (Sel::key / SEL_CTX_VALID): one context character either side, i.e. batches at distance <= 1 (DICEY_NO_DIRECT_CTX: tests)
-      direct_ctx = (with_ctx && keys_on && ix->view.K >= SAX_POST_OFF && ix->view.K + 1 <= SAX_POST_OFF + SAX_POST_N) ? 1u : 0u;
-      // the record that shares a kept string's slot names its group: the packed leaf (qs behind 28 bytes) or the grouped leaf (qs first)
-      const u8* slot_qs = packed ? (const u8*)ws[WS_LEAFG].p + offsetof(PLeaf, qs) : (const u8*)ws[WS_LEAFG].p + offsetof(Leaf, qs);
-      const u32 slot_stride = packed ? (u32)sizeof(PLeaf) : (u32)sizeof(Leaf);
-      hipLaunchKernelGGL(k_locate, dim3(ceil_div(flat_slots + (generic_on ? leaf_slots : 0), TB)), dim3(TB), 0, st, ix->view, (const Sel*)sel_all, slot_qs,
-                         slot_stride, (const u64*)grp_off, (const u32*)nsel, ngrp, (const u64*)hit_off, ws[WS_SEEDS].as<HitSeed>(), ctr, hit_cap, lj,
-                         flat_slots, flat_cap, (u32)generic_on, (u32)jobs_on, direct_ctx);
-      // The job kernels (strings of more than 16 occurrences) are launched when the previous batch of this handle queued any job;
-      // k_locate queues and counts whether or not they run, and a batch that had jobs after one that had none is repeated with
-      // them (the same device as for capacity guesses).  Uniform batches on a genome without repeats never launch them.
-      if (jobs_on) {
-        hipLaunchKernelGGL(k_locate_small, dim3(8192), dim3(64), 0, st, ix->view, lj, ws[WS_SEEDS].as<HitSeed>(), ctr, with_ctx);
-        if (topk) {
-          if (lj.mid_max)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_locate_topk<TOPK_KCAP_MID>), dim3(1280), dim3(256), 0, st, ix->view, lj, (u32)JL_MID,
-                               ws[WS_SEEDS].as<HitSeed>(), ctr, with_ctx);
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_locate_topk<TOPK_KCAP>), dim3(768), dim3(256), 0, st, ix->view, lj, (u32)JL_BIG,
-                             ws[WS_SEEDS].as<HitSeed>(), ctr, with_ctx);
-        }
-        if (!topk || p->max_locations > TOPK_KMAX)
-          hipLaunchKernelGGL(k_locate_big, dim3(1024), dim3(256), 0, st, ix->view, lj, ws[WS_SEEDS].as<HitSeed>(), ctr, topk ? TOPK_KMAX : 0u);
-      }
-      if (!sw.dump_jobs.empty()) {  // development aid: the regions' fill counts, before the summary kernel clears them
-        dump_cnt.assign(3 * JOB_SHARDS, 0);
-        DG_HIP(hipMemcpyAsync(dump_cnt.data(), ctr->job_cnt, sizeof(u32) * 3 * JOB_SHARDS, hipMemcpyDeviceToHost, st));
-      }
-    }
-    if (phase_events) DG_HIP(hipEventRecord(ix->ev[6], st));
-    if (sx) {
-      DG_TRY(launch_site_stage(ix, sx, b, ws[WS_SEEDS].as<HitSeed>(), hit_off, hit_cap, ws[WS_CUM].as<u64>(), nseq, dmax_eff, maxlen, ctr));
-    } else {
-      VerifyArgs va;
-      va.seeds = ws[WS_SEEDS].as<HitSeed>();
-      va.nhits = hit_off + nq;
-      va.hit_cap = hit_cap;
-      va.cum = ws[WS_CUM].as<u64>();
-      va.nseq = nseq;
-      va.hits = ws[WS_HITS].as<dg_hit>();
-      va.refalign = ws[WS_ALN].as<char>();
-      va.queryalign = ws[WS_ALN].as<char>() + (hit_cap + 1) * (u64)stride;
-      va.stride = stride;
-      va.ops = ws[WS_OPS].as<u32>();
-      va.ops_per_hit = ops_per_hit;
-      va.chits = nullptr;
-      va.selkey = direct_ctx ? (const u64*)ws[WS_SELKEY].p : nullptr;
-      va.debug = (sw.exp_bits >> 4) & 3u;  // (DICEY_EXP bits 4-5, measurement aid: verify without its alignments / without the hits' context)
-      const u32 cells = (maxlen + 3 * dmax_eff + 1) * (maxlen + 1);
-      const u32 VT = 128;
-      const dim3 vgrid(ceil_div(hit_cap, VT)), vblock(VT);
-      if (band_verify) {
-        va.chits = d_chits;  // the banded kernel writes compact records itself
-        // hits per lane: 1 while a query has a handful of hits (every window is its own class: nothing to share, smallest LDS
-        // footprint), 8 when the previous batch had dozens of hits per query (repeat families: ~240 hits per kept string)
-        const int ch_env = sw.verify_ch;
-        const u64 per_q = hit_cap / std::max<u64>(nq, 1);
-        // (distance 2 on an i.i.d. genome: 59 hits per query from ~50 strings — nothing to share, and the wider trace of 13 diagonals
-        //  leaves room for fewer workgroups: r03 measured 2.39 ms with 8 hits per lane against 1.83 ms for the lane-per-hit kernel)
-        const u64 share_at = dmax_eff > 1 ? 192 : 24;
-        // r06: with the hits' context in their seeds (FmView::sax) the kernel no longer waits for a text line per hit, and what it
-        // answers to is residency: 4 hits per lane leave room for four workgroups per CU, 8 for two (one batch at a time on the
-        // repeats genome, verify: 0.61 ms with 8, 0.48 ms with 4)
-        const int ch_rich = (with_ctx_hits && dmax_eff <= 1) ? 4 : 8;
-        const int ch = ch_env == 1 || ch_env == 4 || ch_env == 8 ? ch_env : (per_q >= share_at ? ch_rich : (per_q >= share_at / 2 ? 4 : 1));
-        const u32 rows = maxlen + 3 * dmax_eff + 2;
-        const bool wide = dmax_eff > 1;
-        const u32 nw_bytes = ((rows * 256 * (wide ? 4u : 2u) + 7u) & ~7u) + 6u * 256u * 8u, hash_bytes = 2u * 256u * (u32)ch * 10u;
-        const u32 lds = std::max(nw_bytes, hash_bytes);
-        const dim3 mgrid(ceil_div(hit_cap, (u64)256 * ch)), mblock(256);
-        verify_form = ((wide ? 13u : 7u) << 8) | (u32)ch;
-#define DG_LAUNCH_MEMO(WBV, CHV) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify_memo<WBV, CHV>), mgrid, mblock, lds, st, ix->view, b, va, ctr, rows)
-        if (!wide) {
-          if (ch == 8) DG_LAUNCH_MEMO(7, 8);
-          else if (ch == 4) DG_LAUNCH_MEMO(7, 4);
-          else DG_LAUNCH_MEMO(7, 1);
-        } else {
-          if (ch == 8) DG_LAUNCH_MEMO(13, 8);
-          else if (ch == 4) DG_LAUNCH_MEMO(13, 4);
-          else DG_LAUNCH_MEMO(13, 1);
-        }
-#undef DG_LAUNCH_MEMO
-      } else {
-        if (maxlen > MAX_QLEN) {
-          const u32 rows_cap = maxlen + 3 * dmax_eff + 2;
-          const u64 tbytes = (hit_cap + 1) * (u64)rows_cap * 8;
-          if (tbytes > (64ull << 30))
-            return fail(DG_ELIMIT, "a batch with a %u nt query and room for %llu hits needs %llu GB of trace; pass long queries in smaller batches",
-                        maxlen, (unsigned long long)hit_cap, (unsigned long long)(tbytes >> 30));
-          DG_TRY(ws[WS_DP].reserve(tbytes + 64));
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify_long<6 * DMAX + 1>), dim3(ceil_div(hit_cap, 64)), dim3(64), 0, st, ix->view, b, va, ctr,
-                             ws[WS_DP].as<u64>(), rows_cap);
-        } else if (maxlen <= 24) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify<1, true, 24>), vgrid, vblock, 0, st, ix->view, b, va, ctr);
-        else if (maxlen <= 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify<1, true, 32>), vgrid, vblock, 0, st, ix->view, b, va, ctr);
-        else if (cells <= 32 * 160) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify<160, false>), vgrid, vblock, 0, st, ix->view, b, va, ctr);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify<2200, false>), vgrid, vblock, 0, st, ix->view, b, va, ctr);
-        if (ops_per_hit) hipLaunchKernelGGL(k_rows_to_ops, dim3(ceil_div(hit_cap, 256)), dim3(256), 0, st, va, ctr);
-        if (compact) {
-          va.chits = d_chits;
-          hipLaunchKernelGGL(k_hits_to_compact, dim3(ceil_div(hit_cap, 256)), dim3(256), 0, st, va, (const Counters*)ctr);
-        }
-      }
-    }
-    DG_HIP(hipEventRecord(ix->ev[7], st));
-    }
-    hipLaunchKernelGGL(k_summary_block, dim3(1), dim3(NSHARD), 0, st, ctr, (const u64*)(hit_off + nq), &hsum);
-    if (fetch && !group_counts && !sx && ix->fetch_hits_hint) {
-      const u64 capn = std::min<u64>(hit_cap, ix->fetch_hits_hint);
-      if (!spec.pb || spec_cap != capn) {
-        if (spec.pb) pinned_pool().put(spec.pb);
-        spec.pb = pinned_pool().get(fetch_layout(capn).bytes);
-        spec_cap = capn;
-      }
-      if (spec.pb) DG_TRY(queue_fetch(spec.pb, capn));
-    }
-    if (host_timing) t_launched = host_us();
-    DG_HIP(hipStreamSynchronize(st));  // the only synchronisation of a batch
-    DG_HIP(hipGetLastError());
-    if (host_timing) t_synced = host_us();
-    ix->ctr_clean = ctr;  // batch_finish left the counters zeroed where they are
-    ix->ctr_clean_gen = ws[WS_GRP].gen;
-    if (hsum.too_long)
-    return fail(DG_EINVAL, "%llu queries are longer than the %u nt this batch was sized for%s", hsum.too_long, maxlen,
-                p->max_query_len ? " (dg_hunt_params::max_query_len is not an upper bound of this batch, or its offsets decrease)" : "");
-    if (hsum.refused)
-      return fail(DG_EINVAL, "internal error: %llu quer%s could reach the maxNeighborhood cap (%u) without having been enumerated on the host",
-                  hsum.refused, hsum.refused == 1 ? "y" : "ies", p->max_neighborhood);
-    if (const char* dj = (sw.dump_jobs.empty() || dump_cnt.empty()) ? nullptr : sw.dump_jobs.c_str()) {  // development aid: (lo, occs, take, len) of the batch's locate jobs, list after list
-      if (FILE* fj = std::fopen(dj, "wb")) {
-        std::vector<BigJob> hj;
-        for (u32 l = 0; l < 3; ++l)
-          for (u32 sh = 0; sh < JOB_SHARDS; ++sh) {
-            const u32 c = std::min(dump_cnt[l * JOB_SHARDS + sh], job_shard_cap);
-            if (!c) continue;
-            hj.resize(c);
-            DG_HIP(hipMemcpy(hj.data(), ws[WS_JOBS].as<BigJob>() + ((u64)l * JOB_SHARDS + sh) * job_shard_cap, (size_t)c * sizeof(BigJob), hipMemcpyDeviceToHost));
-            for (const BigJob& j : hj) {
-              const u32 rec[4] = {j.lo, j.occs, j.take, j.len | (l << 28)};
-              std::fwrite(rec, 4, 4, fj);
-            }
-          }
-        std::fclose(fj);
-      }
-    }
-#ifdef DG_TOPK_PROFILE
-    {
-      static const char* nm[24] = {"mid.jobs", "mid.load", "mid.threshold", "mid.keys", "mid.sort", "mid.write", "mid.levels", "mid.total",
-                                   "big.jobs", "big.load", "big.threshold", "big.keys", "big.sort", "big.write", "big.levels", "big.total",
-                                   "small.jobs", "small.load", "small.sort", "small.write", "small.total", "-", "-", "-"};
-      std::fprintf(stderr, "topk profile (us summed over workgroups):");
-      for (int i = 0; i < 21; ++i) std::fprintf(stderr, " %s=%.1f", nm[i], (i % 8 == 0 && i < 17) ? (double)hsum.prof[i] : hsum.prof[i] * 0.01);
-      std::fprintf(stderr, "\n");
-    }
-#endif
-    nleaf = hsum.nleaf;
-    nhits = hsum.nhits;
-    // Everything this attempt found wanting is put right before the batch is repeated (one repeat usually serves several causes).
-    bool again = false;
-    // the generic kernels were left out, and the batch had work for them after all (queries with N, longer than 31 nt, a workgroup
-    // of k_search1s whose strings did not fit its LDS list): once more, with them
-    if (fused && !generic_on && (hsum.nleaf > 0 || hsum.n_generic > 0)) {
-      ix->generic_hint = true;
-      force_generic = true;
-      again = true;
-    }
-    if (!walker_on && hsum.n_generic > 0) {  // edit distance 2: groups for the walker after all
-      ix->generic_hint = true;
-      ix->generic_sticky = 8;
-      force_generic = true;
-      again = true;
-    }
-    if (long2 && hsum.n_short2 > 0) {  // queries too short for the LONG2 body went to the walker (or to nobody): once more with the r04 body
-      ix->short2_sticky = 8;
-      force_short2 = true;
-      again = true;
-    }
-    if (!jobs_on && !group_counts && (hsum.jobs_small > 0 || hsum.jobs_big > 0)) {  // strings were queued and nobody served them
-      ix->jobs_hint = true;
-      force_jobs = true;
-      again = true;
-    }
-    const u32 worst = (u32)hsum.worst_shard;
-    if (worst > shard_cap) {
-      shard_cap = worst + worst / 4 + 64;
-      again = true;
-    }
-    if (fused && hsum.worst_sel > flat_cap) {
-      flat_req = (u32)(hsum.worst_sel + hsum.worst_sel / 4 + 64);
-      again = true;
-    }
-    if (!(hsum.overflow & 1) && nhits > hit_cap) {  // (after a buffer overflow the hit count is not this batch's)
-      hit_cap = nhits + nhits / 4 + 1024;
-      again = true;
-    }
-    if (hsum.overflow & 8u) {  // the walker's group list was too short
-      walk_cap = std::min<u64>(ngrp, hsum.n_walk + hsum.n_walk / 4 + 4096);
-      again = true;
-    }
-    ix->walk_hint = (u32)std::min<u64>(hsum.n_walk, 0xFFFFFFFFull);
-    if (again) continue;
-    // The hints are sticky: a kernel family that a batch needed stays on for the next eight batches of the handle, so that a stream
-    // that alternates (chunks with and without N-containing queries, with and without repeat-rich strings) does not pay a repeated
-    // batch at every change (r03 advice; r04 repeats genome: 4 of 14 rotating steps ran twice).
-    if (b.fast2K && !fused) {
-      if (hsum.n_generic > 0 || nxs > 0) ix->generic_sticky = 8;
-      else if (ix->generic_sticky) --ix->generic_sticky;
-      ix->generic_hint = ix->generic_sticky > 0;
-    }
-    if (fused) {
-      if (hsum.nleaf > 0 || hsum.n_generic > 0 || nxs > 0) ix->generic_sticky = 8;
-      else if (ix->generic_sticky) --ix->generic_sticky;
-      ix->generic_hint = ix->generic_sticky > 0;
-    }
-    if (hsum.n_nwin) ix->nwin_sticky = 8;
-    else if (ix->nwin_sticky) --ix->nwin_sticky;
-    if (b.fast2K && !long2 && ix->short2_sticky && !force_short2) --ix->short2_sticky;  // (eight batches on the r04 body, then LONG2 is tried again)
-    if (!group_counts) {
-      if (hsum.jobs_small > 0 || hsum.jobs_big > 0) ix->jobs_sticky = 8;
-      else if (ix->jobs_sticky) --ix->jobs_sticky;
-      ix->jobs_hint = ix->jobs_sticky > 0;
-    }
-    break;
+    if (!at.prep_in)
+      hipLaunchKernelGGL(k_take, dim3(ceil_div(pl.nq * 16, 256)), dim3(256), 0, st, b, (const u64*)grp_off, (const u32*)bf.selbase, bf.flat_slots,
+                         (const u32*)nsel, bf.sel_all, bf.qhits, ctr);
+  } else {
+    hipLaunchKernelGGL(k_group, dim3(ceil_div(leaf_slots, TB)), dim3(TB), 0, st, ws[WS_LEAF].as<Leaf>(), at.shard_cap, ctr, grp_off,
+                       ws[WS_LEAFG].as<Leaf>());
+    u32* scr_rank = ws[WS_SCR].as<u32>();
+    u8* scr_keep = (u8*)(scr_rank + leaf_slots + 1);
+    hipLaunchKernelGGL(k_select, dim3(ceil_div(pl.nq, 64)), dim3(64), 0, st, b, ws[WS_LEAFG].as<Leaf>(), grp_off, bf.sel_gen, nsel, bf.qhits, scr_keep,
+                       scr_rank, ctr);
   }
-  ix->shard_cap_hint = shard_cap;
-  if ((b.fastK || b.fast2K) && hsum.worst_sel) ix->flat_cap_hint = (u32)std::max<unsigned long long>(ix->flat_cap_hint, hsum.worst_sel + hsum.worst_sel / 4 + 64);
-  ix->jobs_big_hint = hsum.jobs_big;
-  if (b.fastK) ix->fused_leaves_hint = hsum.fused_leaves + nleaf;
-  ix->hit_cap_hint = std::max<u64>(ix->hit_cap_hint, nhits + nhits / 4 + 1024);
-  if (group_counts) {
-    DG_HIP(hipMemcpyAsync(group_counts, ws[WS_HITS].p, ngrp * 8, hipMemcpyDeviceToHost, st));
-    DG_HIP(hipStreamSynchronize(st));
-  }
+  if (pl.phase_events) DG_HIP(hipEventRecord(ix->ev[EV_SELECTED], st));
+  return DG_OK;
+}
 
-  if (hsum.overflow & 2)
-    return fail(DG_EHIP, "internal error: an alignment left the band its hit guarantees (or needs more than %u edit columns)", ops_per_hit);
-  dg_hunt_result* R = new dg_hunt_result;
-  std::memset(R, 0, sizeof *R);
-  R->nq = nq;
-  R->nhits = nhits;
-  R->ops_per_hit = ops_per_hit;
-  *out = R;
-  if (fetch) {
-    PinnedBlock* pb = nullptr;
-    u64 capn = 0;
-    if (spec.pb && nhits <= spec_cap) {  // everything is on the host already
-      pb = spec.pb;
-      capn = spec_cap;
-      spec.pb = nullptr;
-    } else {
-      capn = nhits;
-      pb = pinned_pool().get(fetch_layout(capn).bytes);
-      if (!pb) {
-        delete R;
-        *out = nullptr;
-        return fail(DG_ENOMEM, "cannot allocate %llu bytes of pinned host memory for the results", (unsigned long long)fetch_layout(capn).bytes);
+// Count mode (`dicey padlock`): per (query, strand) the occurrences summed over the kept strings, in WS_HITS; no locate, no verify
+static int launch_count(dg_index* ix, const BatchPlan& pl, BatchBufs& bf) {
+  hipStream_t st = ix->stream;
+  const u64 ngrp = pl.ngrp;
+  DG_TRY(ix->ws[WS_HITS].reserve(ngrp * 8 + 64));
+  hipLaunchKernelGGL(k_group_count, dim3(ceil_div(ngrp, TB)), dim3(TB), 0, st, (const u64*)bf.grp_off, (const u32*)bf.selbase, bf.flat_slots,
+                     (const u32*)bf.nsel, (const Sel*)bf.sel_all, ngrp, ix->ws[WS_HITS].as<u64>(), bf.ctr);
+  DG_HIP(hipMemsetAsync(bf.hit_off + pl.nq, 0, 8, st));  // no hits in this mode
+  for (int e = EV_HITS_SCANNED; e <= EV_END; ++e)
+    if (pl.phase_events || e == EV_END) DG_HIP(hipEventRecord(ix->ev[e], st));
+  return DG_OK;
+}
+
+// development aid (DICEY_DUMP_JOBS): the job regions' fill counts, copied before the summary kernel clears them ...
+static int queue_job_dump(dg_index* ix, const BatchBufs& bf, std::vector<u32>& dump_cnt) {
+  if (ix->sw.dump_jobs.empty()) return DG_OK;
+  dump_cnt.assign(3 * JOB_SHARDS, 0);
+  DG_HIP(hipMemcpyAsync(dump_cnt.data(), bf.ctr->job_cnt, sizeof(u32) * 3 * JOB_SHARDS, hipMemcpyDeviceToHost, ix->stream));
+  return DG_OK;
+}
+// ... and, after the batch's synchronisation, (lo, occs, take, len) of the batch's locate jobs into the named file, list after list
+static int write_job_dump(dg_index* ix, const BatchBufs& bf, const std::vector<u32>& dump_cnt) {
+  if (ix->sw.dump_jobs.empty() || dump_cnt.empty()) return DG_OK;
+  FILE* fj = std::fopen(ix->sw.dump_jobs.c_str(), "wb");
+  if (!fj) return DG_OK;
+  std::vector<BigJob> hj;
+  for (u32 l = 0; l < 3; ++l)
+    for (u32 sh = 0; sh < JOB_SHARDS; ++sh) {
+      const u32 c = std::min(dump_cnt[l * JOB_SHARDS + sh], bf.job_shard_cap);
+      if (!c) continue;
+      hj.resize(c);
+      DG_HIP(hipMemcpy(hj.data(), ix->ws[WS_JOBS].as<BigJob>() + ((u64)l * JOB_SHARDS + sh) * bf.job_shard_cap, (size_t)c * sizeof(BigJob), hipMemcpyDeviceToHost));
+      for (const BigJob& j : hj) {
+        const u32 rec[4] = {j.lo, j.occs, j.take, j.len | (l << 28)};
+        std::fwrite(rec, 4, 4, fj);
       }
-      R->owner_ = pb;  // released with the result on the error paths below
-      DG_TRY(queue_fetch(pb, capn));
-      DG_HIP(hipStreamSynchronize(st));
-      DG_HIP(hipGetLastError());
     }
-    R->owner_ = pb;
-    const FetchLayout L = fetch_layout(capn);
-    u8* hb = (u8*)pb->p;
-    if (compact) {
-      R->compact = 1;
-      R->hit_off = (uint64_t*)(hb + L.o_hit_off);
-      const u32* qh = (const u32*)(hb + L.o_qoff);
-      u64 run2 = 0;
-      for (size_t i = 0; i < nq; ++i) {
-        R->hit_off[i] = run2;
-        run2 += qh[i];
-      }
-      R->hit_off[nq] = run2;
-      if (run2 != nhits) return fail(DG_EHIP, "internal error: per-query hit counts add up to %llu, the batch has %llu hits", (unsigned long long)run2, (unsigned long long)nhits);
-      R->qinfo = (uint32_t*)(hb + L.o_meta);
-      R->chits = (uint32_t*)(hb + L.o_hits);
-      R->nseq = nseq;
-      R->seq_start = (uint64_t*)std::malloc(std::max<size_t>(1, nseq) * 8);
-      if (!R->seq_start) return fail(DG_ENOMEM, "out of host memory");
-      std::memcpy(R->seq_start, cum.data(), (size_t)nseq * 8);
-      ix->fetch_hits_hint = nhits + nhits / 32 + 1024;
-    } else {
-    if (caller_qoff) std::memcpy(hb + L.o_qoff, caller_qoff, (nq + 1) * 8);
-    R->hit_off = (uint64_t*)(hb + L.o_hit_off);
+  std::fclose(fj);
+  return DG_OK;
+}
+
+// Locate stage: hit offsets per query, then the `take` smallest suffix-array values of each kept string
+static int launch_locate(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBufs& bf, std::vector<u32>& dump_cnt) {
+  hipStream_t st = ix->stream;
+  auto& ws = ix->ws;
+  Counters* ctr = bf.ctr;
+  DG_TRY(device_scan(st, bf.qhits, pl.nq, bf.hit_off, bf.scan_buf));
+  if (pl.phase_events) DG_HIP(hipEventRecord(ix->ev[EV_HITS_SCANNED], st));
+  // strings with many occurrences go to three job lists: up to 256 occurrences for a wavefront each, more for a workgroup each
+  // (those that fit the small buffer of k_locate_topk whole, and the rest)
+  at.jobs_on = ix->jobs_hint || at.force_jobs || pl.p->max_locations > TOPK_KMAX;
+  // repeat-rich strings: up to TOPK_KMAX positions through the block minima, more (hunt -m above 1 024) by radix passes
+  const bool topk = ix->view.nlev > 1;
+  // A batch with thousands of repeat-rich strings (the previous batch of this handle tells): intervals up to 4 608 entries go
+  // to the small-buffer form of k_locate_topk.  (r03 also ran the three job kernels side by side on helper streams: each
+  // slowed down by what the others took — 114 / 220 / 228 us alone, 220 / 494 / 268 us together — and the stage gained
+  // 0.08 of 0.91 ms; not worth two more streams per handle.)
+  const bool rich = topk && ix->jobs_big_hint >= 2048;
+  LocJobs lj;
+  for (int l = 0; l < 3; ++l) lj.list[l] = ws[WS_JOBS].as<BigJob>() + (u64)l * JOB_SHARDS * bf.job_shard_cap;
+  lj.shard_cap = bf.job_shard_cap;
+  lj.cnt = ctr->job_cnt;
+  lj.mid_max = rich ? 8 * TOPK_KCAP_MID : 0u;
+  const u32 with_ctx = at.with_ctx_hits ? 1u : 0u;
+  // r06: the same for a string with ONE occurrence that k_locate serves itself, when the search kernel knew the character in front
+  // of it (Sel::key / SEL_CTX_VALID): one context character either side, i.e. batches at distance <= 1 (DICEY_NO_DIRECT_CTX: tests)
+  at.direct_ctx = (with_ctx && at.keys_on && ix->view.K >= SAX_POST_OFF && ix->view.K + 1 <= SAX_POST_OFF + SAX_POST_N) ? 1u : 0u;
+  // the record that shares a kept string's slot names its group: the packed leaf (qs behind 28 bytes) or the grouped leaf (qs first)
+  const u8* slot_qs = pl.packed ? (const u8*)ws[WS_LEAFG].p + offsetof(PLeaf, qs) : (const u8*)ws[WS_LEAFG].p + offsetof(Leaf, qs);
+  const u32 slot_stride = pl.packed ? (u32)sizeof(PLeaf) : (u32)sizeof(Leaf);
+  hipLaunchKernelGGL(k_locate, dim3(ceil_div(bf.flat_slots + (at.generic_on ? bf.leaf_slots : 0), TB)), dim3(TB), 0, st, ix->view, (const Sel*)bf.sel_all,
+                     slot_qs, slot_stride, (const u64*)bf.grp_off, (const u32*)bf.nsel, pl.ngrp, (const u64*)bf.hit_off, ws[WS_SEEDS].as<HitSeed>(), ctr,
+                     at.hit_cap, lj, bf.flat_slots, at.flat_cap, (u32)at.generic_on, (u32)at.jobs_on, at.direct_ctx);
+  // The job kernels (strings of more than 16 occurrences) are launched when the previous batch of this handle queued any job;
+  // k_locate queues and counts whether or not they run, and a batch that had jobs after one that had none is repeated with
+  // them (the same device as for capacity guesses).  Uniform batches on a genome without repeats never launch them.
+  if (at.jobs_on) {
+    hipLaunchKernelGGL(k_locate_small, dim3(8192), dim3(64), 0, st, ix->view, lj, ws[WS_SEEDS].as<HitSeed>(), ctr, with_ctx);
+    if (topk) {
+      if (lj.mid_max)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_locate_topk<TOPK_KCAP_MID>), dim3(1280), dim3(256), 0, st, ix->view, lj, (u32)JL_MID,
+                           ws[WS_SEEDS].as<HitSeed>(), ctr, with_ctx);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_locate_topk<TOPK_KCAP>), dim3(768), dim3(256), 0, st, ix->view, lj, (u32)JL_BIG, ws[WS_SEEDS].as<HitSeed>(),
+                         ctr, with_ctx);
+    }
+    if (!topk || pl.p->max_locations > TOPK_KMAX)
+      hipLaunchKernelGGL(k_locate_big, dim3(1024), dim3(256), 0, st, ix->view, lj, ws[WS_SEEDS].as<HitSeed>(), ctr, topk ? TOPK_KMAX : 0u);
+  }
+  DG_TRY(queue_job_dump(ix, bf, dump_cnt));
+  if (pl.phase_events) DG_HIP(hipEventRecord(ix->ev[EV_LOCATED], st));
+  return DG_OK;
+}
+
+// queries up to 32 nt, distance <= 2: the banded kernel, which writes compact records itself
+static void launch_verify_memo(dg_index* ix, const BatchPlan& pl, Attempt& at, const BatchBufs& bf, VerifyArgs& va) {
+  hipStream_t st = ix->stream;
+  const Batch& b = bf.b;
+  Counters* ctr = bf.ctr;
+  const u32 maxlen = pl.maxlen, dmax_eff = pl.dmax_eff;
+  const u64 hit_cap = at.hit_cap;
+  va.chits = bf.d_chits;
+  // hits per lane: 1 while a query has a handful of hits (every window is its own class: nothing to share, smallest LDS
+  // footprint), 8 when the previous batch had dozens of hits per query (repeat families: ~240 hits per kept string)
+  const int ch_env = ix->sw.verify_ch;
+  const u64 per_q = hit_cap / std::max<u64>(pl.nq, 1);
+  // (distance 2 on an i.i.d. genome: 59 hits per query from ~50 strings — nothing to share, and the wider trace of 13 diagonals
+  //  leaves room for fewer workgroups: r03 measured 2.39 ms with 8 hits per lane against 1.83 ms for the lane-per-hit kernel)
+  const u64 share_at = dmax_eff > 1 ? 192 : 24;
+  // r06: with the hits' context in their seeds (FmView::sax) the kernel no longer waits for a text line per hit, and what it
+  // answers to is residency: 4 hits per lane leave room for four workgroups per CU, 8 for two (one batch at a time on the
+  // repeats genome, verify: 0.61 ms with 8, 0.48 ms with 4)
+  const int ch_rich = (at.with_ctx_hits && dmax_eff <= 1) ? 4 : 8;
+  const int ch = ch_env == 1 || ch_env == 4 || ch_env == 8 ? ch_env : (per_q >= share_at ? ch_rich : (per_q >= share_at / 2 ? 4 : 1));
+  const u32 rows = maxlen + 3 * dmax_eff + 2;
+  const bool wide = dmax_eff > 1;
+  const u32 nw_bytes = ((rows * 256 * (wide ? 4u : 2u) + 7u) & ~7u) + 6u * 256u * 8u, hash_bytes = 2u * 256u * (u32)ch * 10u;
+  const u32 lds = std::max(nw_bytes, hash_bytes);
+  const dim3 mgrid(ceil_div(hit_cap, (u64)256 * ch)), mblock(256);
+  at.verify_form = ((wide ? 13u : 7u) << 8) | (u32)ch;
+  with_flag(wide, [&](auto W) {
+    with_value<8, 4, 1>((u32)ch, [&](auto C) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify_memo<decltype(W)::value ? 13 : 7, (int)decltype(C)::value>), mgrid, mblock, lds, st, ix->view, b, va, ctr, rows);
+    });
+  });
+}
+
+// every other batch: full-matrix or long-query kernel (character rows), then the rows as operation words and compact records
+static int launch_verify_full(dg_index* ix, const BatchPlan& pl, const Attempt& at, const BatchBufs& bf, VerifyArgs& va) {
+  hipStream_t st = ix->stream;
+  const Batch& b = bf.b;
+  Counters* ctr = bf.ctr;
+  const u32 maxlen = pl.maxlen, dmax_eff = pl.dmax_eff;
+  const u64 hit_cap = at.hit_cap;
+  const u32 cells = (maxlen + 3 * dmax_eff + 1) * (maxlen + 1);
+  const u32 VT = 128;
+  const dim3 vgrid(ceil_div(hit_cap, VT)), vblock(VT);
+  if (maxlen > MAX_QLEN) {
+    const u32 rows_cap = maxlen + 3 * dmax_eff + 2;
+    const u64 tbytes = (hit_cap + 1) * (u64)rows_cap * 8;
+    if (tbytes > (64ull << 30))
+      return fail(DG_ELIMIT, "a batch with a %u nt query and room for %llu hits needs %llu GB of trace; pass long queries in smaller batches", maxlen,
+                  (unsigned long long)hit_cap, (unsigned long long)(tbytes >> 30));
+    DG_TRY(ix->ws[WS_DP].reserve(tbytes + 64));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify_long<6 * DMAX + 1>), dim3(ceil_div(hit_cap, 64)), dim3(64), 0, st, ix->view, b, va, ctr,
+                       ix->ws[WS_DP].as<u64>(), rows_cap);
+  } else if (maxlen <= 24) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify<1, true, 24>), vgrid, vblock, 0, st, ix->view, b, va, ctr);
+  else if (maxlen <= 32) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify<1, true, 32>), vgrid, vblock, 0, st, ix->view, b, va, ctr);
+  else if (cells <= 32 * 160) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify<160, false>), vgrid, vblock, 0, st, ix->view, b, va, ctr);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_verify<2200, false>), vgrid, vblock, 0, st, ix->view, b, va, ctr);
+  if (pl.ops_per_hit) hipLaunchKernelGGL(k_rows_to_ops, dim3(ceil_div(hit_cap, 256)), dim3(256), 0, st, va, ctr);
+  if (pl.compact) {
+    va.chits = bf.d_chits;
+    hipLaunchKernelGGL(k_hits_to_compact, dim3(ceil_div(hit_cap, 256)), dim3(256), 0, st, va, (const Counters*)ctr);
+  }
+  return DG_OK;
+}
+
+// Verify stage: the site stage of `dicey search` in its place, or Needleman-Wunsch on every located hit
+static int launch_verify(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBufs& bf) {
+  auto& ws = ix->ws;
+  if (pl.sx) {
+    DG_TRY(launch_site_stage(ix, pl.sx, bf.b, ws[WS_SEEDS].as<HitSeed>(), bf.hit_off, at.hit_cap, ws[WS_CUM].as<u64>(), pl.nseq, pl.dmax_eff, pl.maxlen,
+                             bf.ctr));
+  } else {
+    VerifyArgs va;
+    va.seeds = ws[WS_SEEDS].as<HitSeed>();
+    va.nhits = bf.hit_off + pl.nq;
+    va.hit_cap = at.hit_cap;
+    va.cum = ws[WS_CUM].as<u64>();
+    va.nseq = pl.nseq;
+    va.hits = ws[WS_HITS].as<dg_hit>();
+    va.refalign = ws[WS_ALN].as<char>();
+    va.queryalign = ws[WS_ALN].as<char>() + (at.hit_cap + 1) * (u64)pl.stride;
+    va.stride = pl.stride;
+    va.ops = ws[WS_OPS].as<u32>();
+    va.ops_per_hit = pl.ops_per_hit;
+    va.chits = nullptr;
+    va.selkey = at.direct_ctx ? (const u64*)ws[WS_SELKEY].p : nullptr;
+    va.debug = (ix->sw.exp_bits >> 4) & 3u;  // (DICEY_EXP bits 4-5, measurement aid: verify without its alignments / without the hits' context)
+    if (pl.band_verify) launch_verify_memo(ix, pl, at, bf, va);
+    else DG_TRY(launch_verify_full(ix, pl, at, bf, va));
+  }
+  DG_HIP(hipEventRecord(ix->ev[EV_END], ix->stream));
+  return DG_OK;
+}
+
+// Fetch: the result's pieces into the pinned block pb, laid out for capn hits.  Compact results lie in the device block as the host
+// holds them; the classic form is packed into one block by k_pack_results first.  One copy either way.
+static int queue_fetch(dg_index* ix, const BatchPlan& pl, const BatchBufs& bf, PinnedBlock* pb, u64 capn) {
+  hipStream_t st = ix->stream;
+  auto& ws = ix->ws;
+  const u64 nq = pl.nq;
+  const FetchLayout L(pl, capn);
+  if (pl.compact) {  // the device block already has the host layout behind hit_off
+    DG_HIP(hipMemcpyAsync((u8*)pb->p + L.o_qoff, ws[WS_PACK].p, L.o_ops - L.o_qoff, hipMemcpyDeviceToHost, st));
+    return DG_OK;
+  }
+  DG_TRY(ws[WS_PACK].reserve(L.bytes + 64));
+  PackArgs pa;
+  const u32* srcs[6] = {reinterpret_cast<const u32*>(bf.hit_off),
+                        pl.caller_qoff ? nullptr : reinterpret_cast<const u32*>(pl.d_qoff),  // the host has its own copy
+                        ws[WS_QMETA].as<u32>() + nq,                                         // qdist, qflags, qnondna lie in this order
+                        ws[WS_QSEQ].as<u32>(), ws[WS_HITS].as<u32>(), ws[WS_OPS].as<u32>()};
+  const u64 offs[6] = {L.o_hit_off, L.o_qoff, L.o_meta, L.o_qseq, L.o_hits, L.o_ops};
+  const u64 words[6] = {(nq + 1) * 2, (nq + 1) * 2, 3 * (u64)nq, (pl.total + 3) / 4, capn * (sizeof(dg_hit) / 4), capn * (u64)pl.ops_per_hit};
+  u64 all = 0;
+  for (int k = 0; k < 6; ++k) {
+    pa.src[k] = srcs[k];
+    pa.dst_word[k] = offs[k] / 4;
+    pa.nwords[k] = words[k];
+    all += words[k];
+  }
+  if (!pl.ops_per_hit) pa.src[5] = nullptr;
+  pa.nhits = bf.hit_off + nq;
+  pa.hit_words = (u32)(sizeof(dg_hit) / 4);
+  pa.op_words = pl.ops_per_hit;
+  hipLaunchKernelGGL(k_pack_results, dim3(ceil_div(all, 256)), dim3(256), 0, st, pa, ws[WS_PACK].as<u32>());
+  DG_HIP(hipMemcpyAsync(pb->p, ws[WS_PACK].p, L.bytes, hipMemcpyDeviceToHost, st));
+  return DG_OK;
+}
+
+// the fetch queued BEHIND the batch's kernels, for as many hits as the handle's previous fetched batch had (plus 3 %)
+static int queue_spec_fetch(dg_index* ix, const BatchPlan& pl, const Attempt& at, const BatchBufs& bf, BlockGuard& spec) {
+  const u64 capn = std::min<u64>(at.hit_cap, ix->fetch_hits_hint);
+  if (!spec.pb || spec.capn != capn) {
+    if (spec.pb) pinned_pool().put(spec.pb);
+    spec.pb = pinned_pool().get(FetchLayout(pl, capn).bytes);
+    spec.capn = capn;
+  }
+  if (spec.pb) DG_TRY(queue_fetch(ix, pl, bf, spec.pb, capn));
+  return DG_OK;
+}
+
+// The result's host pointers, into its pinned block (R->owner_, laid out for capn hits)
+static int fill_result_host(dg_index* ix, const BatchPlan& pl, const std::vector<u64>& cum, u64 capn, dg_hunt_result* R) {
+  const size_t nq = pl.nq;
+  const u64 nhits = R->nhits;
+  const FetchLayout L(pl, capn);
+  u8* hb = (u8*)((PinnedBlock*)R->owner_)->p;
+  R->hit_off = (uint64_t*)(hb + L.o_hit_off);
+  if (pl.compact) {
+    const u32* qh = (const u32*)(hb + L.o_qoff);
+    u64 run2 = 0;
+    for (size_t i = 0; i < nq; ++i) {
+      R->hit_off[i] = run2;
+      run2 += qh[i];
+    }
+    R->hit_off[nq] = run2;
+    if (run2 != nhits) return fail(DG_EHIP, "internal error: per-query hit counts add up to %llu, the batch has %llu hits", (unsigned long long)run2, (unsigned long long)nhits);
+    R->qinfo = (uint32_t*)(hb + L.o_meta);
+    R->chits = (uint32_t*)(hb + L.o_hits);
+    R->nseq = pl.nseq;
+    R->seq_start = (uint64_t*)std::malloc(std::max<size_t>(1, pl.nseq) * 8);
+    if (!R->seq_start) return fail(DG_ENOMEM, "out of host memory");
+    std::memcpy(R->seq_start, cum.data(), (size_t)pl.nseq * 8);
+  } else {
+    if (pl.caller_qoff) std::memcpy(hb + L.o_qoff, pl.caller_qoff, (nq + 1) * 8);
     R->qoff = (uint64_t*)(hb + L.o_qoff);
     R->hits = (dg_hit*)(hb + L.o_hits);
     R->ops = (uint32_t*)(hb + L.o_ops);
@@ -1322,66 +1283,285 @@ int run_batch(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uin
     R->qflags = R->qdistance + nq;
     R->qnondna = R->qflags + nq;
     R->qseq = hb + L.o_qseq;
-    ix->fetch_hits_hint = nhits + nhits / 32 + 1024;
-    }
   }
-  if (compact) {
+  ix->fetch_hits_hint = nhits + nhits / 32 + 1024;
+  return DG_OK;
+}
+
+// Fetch after the batch: the speculative block when it holds every hit, a second copy (and synchronisation) otherwise.
+// Error paths: the block belongs to the result from `R->owner_ = pb` on and is released with it by the caller; only a failed
+// allocation, with nothing to own yet, takes the result back here.
+static int fetch_result(dg_index* ix, const BatchPlan& pl, const BatchBufs& bf, const std::vector<u64>& cum, BlockGuard& spec, dg_hunt_result* R,
+                        dg_hunt_result** out) {
+  u64 capn = 0;
+  if (spec.pb && R->nhits <= spec.capn) {  // everything is on the host already
+    R->owner_ = spec.pb;
+    capn = spec.capn;
+    spec.pb = nullptr;
+  } else {
+    capn = R->nhits;
+    PinnedBlock* pb = pinned_pool().get(FetchLayout(pl, capn).bytes);
+    if (!pb) {
+      delete R;
+      *out = nullptr;
+      return fail(DG_ENOMEM, "cannot allocate %llu bytes of pinned host memory for the results", (unsigned long long)FetchLayout(pl, capn).bytes);
+    }
+    R->owner_ = pb;
+    DG_TRY(queue_fetch(ix, pl, bf, pb, capn));
+    DG_HIP(hipStreamSynchronize(ix->stream));
+    DG_HIP(hipGetLastError());
+  }
+  return fill_result_host(ix, pl, cum, capn, R);
+}
+
+// The result's device pointers (valid until the lane's next batch)
+static void fill_result_device(dg_index* ix, const BatchPlan& pl, dg_hunt_result* R) {
+  auto& ws = ix->ws;
+  if (pl.compact) {
     R->compact = 1;
-    R->d_hits = ws[WS_PACK].as<u32>() + 2 * nq;  // compact records (chit_words each)
+    R->d_hits = ws[WS_PACK].as<u32>() + 2 * pl.nq;  // compact records (chit_words each)
     R->d_ops = nullptr;
     R->d_block = ws[WS_PACK].p;
-    R->d_block_bytes = 8ull * nq + nhits * (u64)chit_words * 4;
+    R->d_block_bytes = 8ull * pl.nq + R->nhits * (u64)pl.chit_words * 4;
   } else {
     R->d_hits = ws[WS_HITS].p;
-    R->d_ops = ops_per_hit ? ws[WS_OPS].p : nullptr;
+    R->d_ops = pl.ops_per_hit ? ws[WS_OPS].p : nullptr;
   }
-  R->stream = (void*)st;
-  R->ctr_leaves = nleaf + hsum.fused_leaves;
+  R->stream = (void*)ix->stream;
+}
+
+// The result's counters, stage times and kernel forms
+static void fill_result_report(dg_index* ix, const BatchPlan& pl, const Attempt& at, const BatchBufs& bf, const CapResult& cr, dg_hunt_result* R) {
+  const Summary& hsum = *bf.hsum;
+  R->ctr_leaves = at.nleaf + hsum.fused_leaves;
   R->ctr_ext_steps = hsum.steps;
   R->ctr_tab_reads = hsum.lookups;
   R->ctr_filter_probes = hsum.probes;
   R->ctr_sa_reads = hsum.sa_reads;
   R->ctr_win_bytes = hsum.win_bytes;
-  R->ms_total = ev_ms(ix->ev[0], ix->ev[7]);
-  R->ms_search_flat = (b.fastK || b.fast2K) ? ev_ms(ix->ev[1], ix->ev[8]) : 0.0;
-  if (phase_events) {
-    R->ms_search = ev_ms(ix->ev[1], ix->ev[2]);
-    R->ms_select = ev_ms(ix->ev[3], ix->ev[4]);
-    R->ms_locate = ev_ms(ix->ev[5], ix->ev[6]);
-    R->ms_verify = ev_ms(ix->ev[6], ix->ev[7]);
+  R->ms_total = ev_ms(ix->ev[EV_BEGIN], ix->ev[EV_END]);
+  R->ms_search_flat = (bf.b.fastK || bf.b.fast2K) ? ev_ms(ix->ev[EV_PREPARED], ix->ev[EV_FLAT_END]) : 0.0;
+  if (pl.phase_events) {
+    R->ms_search = ev_ms(ix->ev[EV_PREPARED], ix->ev[EV_SEARCHED]);
+    R->ms_select = ev_ms(ix->ev[EV_GROUPS_SCANNED], ix->ev[EV_SELECTED]);
+    R->ms_locate = ev_ms(ix->ev[EV_HITS_SCANNED], ix->ev[EV_LOCATED]);
+    R->ms_verify = ev_ms(ix->ev[EV_LOCATED], ix->ev[EV_END]);
   } else R->ms_search = R->ms_search_flat;
-  R->ms_cap = ms_cap;
-  R->cap_queries_device = dev_jobs.size();
-  R->cap_queries_host = cs.looked_at;
-  R->cap_patterns = nxs;
-  R->flat_kernel_form = flat_form;
-  R->verify_kernel_form = verify_form;
+  R->ms_cap = cr.ms_cap;
+  R->cap_queries_device = cr.dev_queries;
+  R->cap_queries_host = cr.looked_at;
+  R->cap_patterns = bf.nxs;
+  R->flat_kernel_form = at.flat_form;
+  R->verify_kernel_form = at.verify_form;
   R->t_base_gen = 0;
   R->t_search_begin_ms = R->t_search_end_ms = 0.0;
-  if (base_ev && (b.fastK || b.fast2K)) {
-    // the two base events are used in turn and re-recorded under the shared record's mutex: a batch that outlived two generations
-    // (cap-prone or very long batches) finds its base re-recorded and reports no interval rather than a wrong one
-    dg_index::SharedHints* shb = ix->shared_hints.load();
-    std::unique_lock<std::mutex> lkb(shb->mu);
-    float t0 = 0.f, t1 = 0.f;
-    if (shb->base_gen - base_gen < 2 && hipEventElapsedTime(&t0, base_ev, ix->ev[1]) == hipSuccess && hipEventElapsedTime(&t1, base_ev, ix->ev[8]) == hipSuccess && t0 >= 0.f) {
-      R->t_search_begin_ms = t0;
-      R->t_search_end_ms = t1;
-      R->t_base_gen = base_gen;
+}
+
+// development builds (DG_TOPK_PROFILE): the phase clocks of the locate job kernels
+static void print_topk_profile(const Summary& hsum) {
+#ifdef DG_TOPK_PROFILE
+  static const char* nm[24] = {"mid.jobs", "mid.load", "mid.threshold", "mid.keys", "mid.sort", "mid.write", "mid.levels", "mid.total",
+                               "big.jobs", "big.load", "big.threshold", "big.keys", "big.sort", "big.write", "big.levels", "big.total",
+                               "small.jobs", "small.load", "small.sort", "small.write", "small.total", "-", "-", "-"};
+  std::fprintf(stderr, "topk profile (us summed over workgroups):");
+  for (int i = 0; i < 21; ++i) std::fprintf(stderr, " %s=%.1f", nm[i], (i % 8 == 0 && i < 17) ? (double)hsum.prof[i] : hsum.prof[i] * 0.01);
+  std::fprintf(stderr, "\n");
+#else
+  (void)hsum;
+#endif
+}
+
+// Everything an attempt found wanting is put right before the batch is repeated (one repeat usually serves several causes).
+// Returns whether the batch runs again.
+static bool review_attempt(const Summary& hsum, const BatchPlan& pl, Attempt& at, dg_index* ix) {
+  at.nleaf = hsum.nleaf;
+  at.nhits = hsum.nhits;
+  bool again = false;
+  // the generic kernels were left out, and the batch had work for them after all (queries with N, longer than 31 nt, a workgroup
+  // of k_search1s whose strings did not fit its LDS list): once more, with them
+  if (at.fused && !at.generic_on && (hsum.nleaf > 0 || hsum.n_generic > 0)) {
+    ix->generic_hint = true;
+    at.force_generic = true;
+    again = true;
+  }
+  if (!at.walker_on && hsum.n_generic > 0) {  // edit distance 2: groups for the walker after all
+    ix->generic_hint = true;
+    ix->generic_sticky = 8;
+    at.force_generic = true;
+    again = true;
+  }
+  if (at.long2 && hsum.n_short2 > 0) {  // queries too short for the LONG2 body went to the walker (or to nobody): once more with the r04 body
+    ix->short2_sticky = 8;
+    at.force_short2 = true;
+    again = true;
+  }
+  if (!at.jobs_on && !pl.group_counts && (hsum.jobs_small > 0 || hsum.jobs_big > 0)) {  // strings were queued and nobody served them
+    ix->jobs_hint = true;
+    at.force_jobs = true;
+    again = true;
+  }
+  const u32 worst = (u32)hsum.worst_shard;
+  if (worst > at.shard_cap) {
+    at.shard_cap = worst + worst / 4 + 64;
+    again = true;
+  }
+  if (at.fused && hsum.worst_sel > at.flat_cap) {
+    at.flat_req = (u32)(hsum.worst_sel + hsum.worst_sel / 4 + 64);
+    again = true;
+  }
+  if (!(hsum.overflow & 1) && at.nhits > at.hit_cap) {  // (after a buffer overflow the hit count is not this batch's)
+    at.hit_cap = at.nhits + at.nhits / 4 + 1024;
+    again = true;
+  }
+  if (hsum.overflow & 8u) {  // the walker's group list was too short
+    at.walk_cap = std::min<u64>(pl.ngrp, hsum.n_walk + hsum.n_walk / 4 + 4096);
+    again = true;
+  }
+  ix->walk_hint = (u32)std::min<u64>(hsum.n_walk, 0xFFFFFFFFull);
+  return again;
+}
+
+// What the handle's next batch starts from, after the attempt that stood.
+// The hints are sticky: a kernel family that a batch needed stays on for the next eight batches of the handle, so that a stream
+// that alternates (chunks with and without N-containing queries, with and without repeat-rich strings) does not pay a repeated
+// batch at every change (r03 advice; r04 repeats genome: 4 of 14 rotating steps ran twice).
+static void settle_hints(const Summary& hsum, const BatchPlan& pl, const Attempt& at, const BatchBufs& bf, dg_index* ix) {
+  const Batch& b = bf.b;
+  if (b.fast2K && !at.fused) {
+    if (hsum.n_generic > 0 || bf.nxs > 0) ix->generic_sticky = 8;
+    else if (ix->generic_sticky) --ix->generic_sticky;
+    ix->generic_hint = ix->generic_sticky > 0;
+  }
+  if (at.fused) {
+    if (hsum.nleaf > 0 || hsum.n_generic > 0 || bf.nxs > 0) ix->generic_sticky = 8;
+    else if (ix->generic_sticky) --ix->generic_sticky;
+    ix->generic_hint = ix->generic_sticky > 0;
+  }
+  if (hsum.n_nwin) ix->nwin_sticky = 8;
+  else if (ix->nwin_sticky) --ix->nwin_sticky;
+  if (b.fast2K && !at.long2 && ix->short2_sticky && !at.force_short2) --ix->short2_sticky;  // (eight batches on the r04 body, then LONG2 is tried again)
+  if (!pl.group_counts) {
+    if (hsum.jobs_small > 0 || hsum.jobs_big > 0) ix->jobs_sticky = 8;
+    else if (ix->jobs_sticky) --ix->jobs_sticky;
+    ix->jobs_hint = ix->jobs_sticky > 0;
+  }
+  ix->shard_cap_hint = at.shard_cap;
+  if ((b.fastK || b.fast2K) && hsum.worst_sel) ix->flat_cap_hint = (u32)std::max<unsigned long long>(ix->flat_cap_hint, hsum.worst_sel + hsum.worst_sel / 4 + 64);
+  ix->jobs_big_hint = hsum.jobs_big;
+  if (b.fastK) ix->fused_leaves_hint = hsum.fused_leaves + at.nleaf;
+  ix->hit_cap_hint = std::max<u64>(ix->hit_cap_hint, at.nhits + at.nhits / 4 + 1024);
+}
+
+// One batch through the five kernels.  All sizes that are only known on the device (number of leaves, number of hits)
+// are handled with capacity guesses that the kernels check themselves; the host synchronises ONCE at the end, and
+// repeats the batch with larger buffers in the rare case a capacity was exceeded.
+// group_counts != nullptr: count mode (`dicey padlock`, padlock.h:396-421) — stop after the select stage and return, per
+// (query, strand), the occurrences summed over the kept neighbourhood strings; no locate, no verify.
+// h_qbytes / h_qoff: the host copy of the queries when the caller has one (needed only when a neighbourhood could reach
+// the cap; read back from the device otherwise).
+//
+// The stages, in order, and the function that runs each:
+//   once per batch   make_plan (limits, what is fixed) -> the fixed workspaces (GrpLayout) -> cap_stage (upload_xs, launch_cap_enum)
+//                    -> init_batch -> upload_seq_starts -> pull_shared_hints -> start_caps
+//   per attempt      decide_attempt -> reserve_attempt -> counters cleared if dirty -> launch_prepare -> launch_search (launch_flat1,
+//                    launch_flat2, launch_walker, launch_nres) -> launch_select -> launch_count, or launch_locate -> launch_verify
+//                    -> k_summary_block -> queue_spec_fetch -> the batch's ONE synchronisation -> review_attempt (again?)
+//   after the last   settle_hints -> fetch_result (fill_result_host) -> fill_result_device -> fill_result_report -> search_interval
+//                    -> push_shared_hints
+int run_batch(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uint32_t nseq, const void* d_qbytes,
+                     const void* d_qoff, size_t nq, u64 total, u32 maxlen, int fetch, dg_hunt_result** out, SearchExtra* sx,
+                     uint64_t* group_counts, const uint8_t* h_qbytes, const uint64_t* h_qoff) {
+  BatchPlan plan;
+  DG_TRY(make_plan(plan, ix->sw, p, nseq, d_qbytes, d_qoff, nq, total, maxlen, fetch, sx, group_counts, h_qoff));
+  DG_HIP(hipSetDevice(ix->device));
+  hipStream_t st = ix->stream;
+  const bool host_timing = ix->sw.host_timing;  // host phases of every batch to stderr (the switches were read by the entry point on the caller's thread)
+  const double t_enter = host_timing ? host_us() : 0.0;
+  double t_launched = 0, t_synced = 0;
+  for (int i = 0; i < EV_COUNT; ++i)
+    if (!ix->ev[i]) DG_HIP(hipEventCreate(&ix->ev[i]));
+  auto& ws = ix->ws;
+  const GrpLayout grp(nq, plan.ngrp, plan.scan_tmp);
+  DG_TRY(ws[WS_FW].reserve(total + 8));
+  DG_TRY(ws[WS_RV].reserve(total + 8));
+  DG_TRY(ws[WS_QSEQ].reserve(total + 8));
+  DG_TRY(ws[WS_QMETA].reserve(nq * 16 + 64));
+  DG_TRY(ws[WS_GINFO].reserve(plan.ngrp * (sizeof(GidInfo) + sizeof(uint4)) + 64));
+  DG_TRY(ws[WS_GRP].reserve(grp.bytes()));
+  DG_TRY(ws[WS_CUM].reserve((u64)nseq * 8 + 8));
+  CapResult cap;
+  DG_TRY(cap_stage(ix, plan, h_qbytes, cap));
+  BatchBufs bf;
+  init_batch(ix, plan, cap, grp, bf);
+  if (!ix->pinned) DG_HIP(hipHostMalloc((void**)&ix->pinned, 4096, 0));
+  bf.hsum = (Summary*)ix->pinned;
+  const Summary& hsum = *bf.hsum;
+  std::vector<u64> cum(nseq);
+  DG_TRY(upload_seq_starts(ix, seqlen, cum));
+
+  u32 base_gen = 0;
+  hipEvent_t base_ev = nullptr;
+  pull_shared_hints(ix, base_gen, base_ev);
+  Attempt at;
+  start_caps(ix, plan, bf.nxs, at);
+  BlockGuard spec;
+  std::vector<u32> dump_cnt;
+  for (int attempt = 0;; ++attempt) {
+    if (attempt > 8)
+      return fail(DG_ENOMEM, "buffer overflow persists (%llu leaves, %llu hits)", (unsigned long long)at.nleaf, (unsigned long long)at.nhits);
+    decide_attempt(ix, plan, bf, at);
+    DG_TRY(reserve_attempt(ix, plan, at, bf));
+    // counters: left zeroed by the previous batch's last kernel (batch_finish) unless they moved or that batch did not finish;
+    // group counters: cleared by k_prepare
+    if (ix->ctr_clean != (const void*)bf.ctr || ix->ctr_clean_gen != ws[WS_GRP].gen)
+      DG_HIP(hipMemsetAsync(grp.zero_from(ws[WS_GRP].p), 0, grp.zero_bytes(), st));
+    ix->ctr_clean = nullptr;  // dirty until this attempt's last kernel has run
+    DG_HIP(hipEventRecord(ix->ev[EV_BEGIN], st));
+    DG_TRY(launch_prepare(ix, plan, at, bf));
+    DG_TRY(launch_search(ix, plan, at, bf));
+    DG_TRY(launch_select(ix, plan, at, bf));
+    if (group_counts) DG_TRY(launch_count(ix, plan, bf));
+    else {
+      DG_TRY(launch_locate(ix, plan, at, bf, dump_cnt));
+      DG_TRY(launch_verify(ix, plan, at, bf));
     }
+    hipLaunchKernelGGL(k_summary_block, dim3(1), dim3(NSHARD), 0, st, bf.ctr, (const u64*)(bf.hit_off + nq), bf.hsum);
+    if (fetch && plan.hunt && ix->fetch_hits_hint) DG_TRY(queue_spec_fetch(ix, plan, at, bf, spec));
+    if (host_timing) t_launched = host_us();
+    DG_HIP(hipStreamSynchronize(st));  // the only synchronisation of a batch
+    DG_HIP(hipGetLastError());
+    if (host_timing) t_synced = host_us();
+    ix->ctr_clean = bf.ctr;  // batch_finish left the counters zeroed where they are
+    ix->ctr_clean_gen = ws[WS_GRP].gen;
+    if (hsum.too_long)
+      return fail(DG_EINVAL, "%llu queries are longer than the %u nt this batch was sized for%s", hsum.too_long, maxlen,
+                  p->max_query_len ? " (dg_hunt_params::max_query_len is not an upper bound of this batch, or its offsets decrease)" : "");
+    if (hsum.refused)
+      return fail(DG_EINVAL, "internal error: %llu quer%s could reach the maxNeighborhood cap (%u) without having been enumerated on the host",
+                  hsum.refused, hsum.refused == 1 ? "y" : "ies", p->max_neighborhood);
+    DG_TRY(write_job_dump(ix, bf, dump_cnt));
+    print_topk_profile(hsum);
+    if (!review_attempt(hsum, plan, at, ix)) break;
   }
-  if (dg_index::SharedHints* sh = ix->shared_hints.load()) {  // for the other lanes' next batches
-    std::lock_guard<std::mutex> lk(sh->mu);
-    sh->shard_cap = std::max(sh->shard_cap, ix->shard_cap_hint);
-    sh->flat_cap = std::max(sh->flat_cap, ix->flat_cap_hint);
-    sh->hit_cap = std::max(sh->hit_cap, ix->hit_cap_hint);
-    sh->fetch_hits = ix->fetch_hits_hint;
-    sh->generic_sticky = ix->generic_sticky;
-    sh->jobs_sticky = ix->jobs_sticky;
-    sh->jobs_big = ix->jobs_big_hint;
-    sh->fused_leaves = ix->fused_leaves_hint;
-    sh->valid = true;
+  settle_hints(hsum, plan, at, bf, ix);
+  if (group_counts) {
+    DG_HIP(hipMemcpyAsync(group_counts, ws[WS_HITS].p, plan.ngrp * 8, hipMemcpyDeviceToHost, st));
+    DG_HIP(hipStreamSynchronize(st));
   }
+
+  if (hsum.overflow & 2)
+    return fail(DG_EHIP, "internal error: an alignment left the band its hit guarantees (or needs more than %u edit columns)", plan.ops_per_hit);
+  dg_hunt_result* R = new dg_hunt_result;
+  std::memset(R, 0, sizeof *R);
+  R->nq = nq;
+  R->nhits = at.nhits;
+  R->ops_per_hit = plan.ops_per_hit;
+  *out = R;
+  if (fetch) DG_TRY(fetch_result(ix, plan, bf, cum, spec, R, out));
+  fill_result_device(ix, plan, R);
+  fill_result_report(ix, plan, at, bf, cap, R);
+  if (base_ev && (bf.b.fastK || bf.b.fast2K)) search_interval(ix, base_gen, base_ev, R);
+  push_shared_hints(ix);
   if (host_timing)
     std::fprintf(stderr, "dicey timing: batch of %zu on stream %p entered at %.0f us: host %.0f us before the synchronisation (last attempt's "
                  "launches included), %.0f us waiting, %.0f us after; device %.3f ms\n", nq, (void*)st, std::fmod(t_enter, 1e8), t_launched - t_enter,

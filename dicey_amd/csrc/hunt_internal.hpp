@@ -98,6 +98,18 @@ struct Counters {
   } while (0)
 #endif
 static constexpr u32 JOB_SHARDS = 64;
+// the words of Counters::pad_ in use: single counters and flags of a batch (k_prepare, k_walk_list -> k_summary_block)
+enum CounterWord : u32 {
+  CW_REFUSED = 1,    // queries whose neighbourhood could reach the cap without having been enumerated (Batch::refused)
+  CW_TOO_LONG = 2,   // queries longer than the batch was sized for (Batch::too_long)
+  CW_N_GENERIC = 6,  // groups searched outside the flat kernels
+  CW_N_NWIN = 7,     // flag: N-bearing strands that walk in window mode (Batch::nwin)
+  CW_N_SHORT2 = 9,   // distance 2: queries too short for k_search2p's LONG2 body (Batch::short2)
+  CW_N_WALK = 10,    // groups listed for the walker (k_walk_list)
+  CW_N_KEEP = 11,    // strands listed for k_nkeep (k_walk_list)
+};
+// dg_index::ev: the events run_batch records on the lane's stream, in stream order except EV_FLAT_END (behind the flat search kernel)
+enum BatchEvent : int { EV_BEGIN = 0, EV_PREPARED, EV_SEARCHED, EV_GROUPS_SCANNED, EV_SELECTED, EV_HITS_SCANNED, EV_LOCATED, EV_END, EV_FLAT_END, EV_COUNT };
 
 struct HitSeed {  // 16 bytes, read as one uint4
   u32 pos;  // text position of the neighbourhood string

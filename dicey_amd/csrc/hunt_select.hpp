@@ -76,16 +76,16 @@ DG_DEV void batch_finish(Counters* ctr, const u64* nhits, Summary* host_out) {
     host_out->probes = acc[6];
     host_out->nhits = *nhits;
     host_out->overflow = ctr->overflow;
-    host_out->refused = ctr->pad_[1];
-    host_out->too_long = ctr->pad_[2];
+    host_out->refused = ctr->pad_[CW_REFUSED];
+    host_out->too_long = ctr->pad_[CW_TOO_LONG];
     host_out->jobs_big = acc[11];
     host_out->jobs_small = acc[10];
     host_out->worst_sel = acc[8];
     host_out->fused_leaves = acc[9];
-    host_out->n_generic = ctr->pad_[6];
-    host_out->n_nwin = ctr->pad_[7];
-    host_out->n_short2 = ctr->pad_[9];
-    host_out->n_walk = ctr->pad_[10] > ctr->pad_[11] ? ctr->pad_[10] : ctr->pad_[11];  // (the longer of the two lists: they share a capacity)
+    host_out->n_generic = ctr->pad_[CW_N_GENERIC];
+    host_out->n_nwin = ctr->pad_[CW_N_NWIN];
+    host_out->n_short2 = ctr->pad_[CW_N_SHORT2];
+    host_out->n_walk = ctr->pad_[CW_N_WALK] > ctr->pad_[CW_N_KEEP] ? ctr->pad_[CW_N_WALK] : ctr->pad_[CW_N_KEEP];  // (the longer of the two lists: they share a capacity)
 #ifdef DG_TOPK_PROFILE
     for (int i = 0; i < 24; ++i) host_out->prof[i] = ctr->prof[i];
 #endif
