@@ -835,6 +835,9 @@ static FlatSel flat_sel(const Attempt& at, const BatchBufs& bf) {
   return fs;
 }
 
+#ifndef DG_FLAT1_LEAVE
+#define DG_FLAT1_LEAVE 1u  // (tools/build_variant.sh <name> -DDG_FLAT1_LEAVE=0u: every wavefront stays to the end, for A/B runs)
+#endif
 // distance 1: the flat kernel takes every query that qualifies, k_search (one lane per strand) the rest
 static int launch_flat1(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBufs& bf, const SearchOut& so) {
   hipStream_t st = ix->stream;
@@ -858,7 +861,10 @@ static int launch_flat1(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBuf
     const u32 lcap_env = sw.fused_lcap ? std::max<u32>(1u, std::min<u32>(FUSED_LCAP, sw.fused_lcap)) : 0u;
     const u32 lcap = lcap_env ? lcap_env : (ix->fused_leaves_hint > 48ull * g1.x ? FUSED_LCAP : FUSED_LCAP / 2);
     const u32 lds1 = fused_lds_bytes(lcap);
-    const u32 leave1 = 1u | (sw.exp_bits << 1);  // bit 0: idle wavefronts end behind the probe phase (r04 A/B on one box: 0.2188 ms with, 0.2194 without — harmless, kept)
+    // bit 0: the leave rule of k_search1s — wavefronts without a queue entry end behind the queue's barrier, the others behind the
+    // dense phase when the queue is short.  (r04's form, "at most 64 entries", measured 0.2188 ms with and 0.2194 without: the queue
+    // held 146 entries per workgroup then, not ~40, and the rule hardly ever fired; it holds the ~38 double survivors now.)
+    const u32 leave1 = DG_FLAT1_LEAVE | (sw.exp_bits << 1);
     PrepOut po;
     po.qhits = bf.qhits;
     with_flag(pl.indel, [&](auto I) {

@@ -639,14 +639,24 @@ struct FlatSel {
   u32* nsel;       // [2 nq]
   u64* key;        // [flat slots] r06: the kept strings themselves (see SEL_CTX_VALID); nullptr = not wanted
 };
-// r04: (i) the three wavefronts that have nothing to do behind the probe phase END there instead of waiting at the barrier behind
-// the dense phase (the usual workgroup has ~40 survivors, one wavefront's worth): the r04a counters showed the kernel resident at
-// 6-7 of 8 wavefronts per SIMD, two thirds of the wave cycles waiting — three of four of those slots held by wavefronts parked at
-// that barrier; (ii) the LDS list is dynamic (lcap entries, 256 by default: 5.6 KB, 512 when the previous batch's workgroups held
+// r04: (i) wavefronts that have nothing to do behind the probe phase END there instead of waiting at the barrier behind the dense
+// phase: the r04a counters showed the kernel resident at 6-7 of 8 wavefronts per SIMD, two thirds of the wave cycles waiting —
+// three of four of those slots held by wavefronts parked at that barrier.  What the counters of the headline batch say about it
+// (r05/r06: 29.06 M filter probes per launch, 26.63 M of them in the probe phase, 16 667 workgroups): 146 candidates per workgroup
+// pass the tail window, not the ~40 this comment used to assume, so "at most 64 entries" almost never held and the rule did
+// nothing (0.2188 against 0.2194 ms).  About 38 of the 146 pass the head window too (832 083 table and pre5 reads per launch).
+// Hence the head window is probed by the candidate's own lane BEFORE the queue: the queue holds double survivors only, one
+// wavefront's worth in the usual workgroup, and the leave rule (`tleave` in the kernel, FUSED_TLEAVE) fires for nearly every workgroup;
+// (ii) the LDS list is dynamic (lcap entries, 256 by default: 5.6 KB, 512 when the previous batch's workgroups held
 // more than ~64 strings on average) and the survivor queue holds 512 entries, filled in rounds when more survive, so that the
 // freed slots can be taken by new workgroups.
 static constexpr u32 FUSED_LCAP = 512;   // largest LDS list
 static constexpr u32 FUSED_QCAP = 512;   // survivor queue entries per round
+// Up to this many queue entries the wavefronts 1-3 end behind the dense phase and the first one selects alone; above it the pair
+// loops of the select stage keep every wavefront that had an entry.  Measured: 256 and 512 cost the repeats genome
+// 6-9 % of its step (a workgroup of 65-512 entries is a repeat family already), 64 costs nothing there — at 64 the bound adds
+// nothing to "a wavefront without an entry ends", which is what the headline's workgroups (~38 entries) live on.
+static constexpr u32 FUSED_TLEAVE = 64;
 static inline u32 fused_lds_bytes(u32 lcap) { return lcap * (8u + 4u + 4u + 2u + 2u + 2u + 2u + 1u); }  // (+ 1: l_ctx, r06)
 // TAKE (r04): the workgroup also does k_take's work for its own queries (the occurrences of a query's kept strings in push order:
 // take = what hunter.h:349-357 still accepts, a saturating prefix sum) — k_take, 12 us of a 0.34 ms step, is not launched.  Used
@@ -659,6 +669,7 @@ struct PrepOut {
 template <bool INDEL, bool TAKE>
 __global__ void __launch_bounds__(256, 8) k_search1s(FmView f, Batch b, SearchOut o, FlatSel fs, u32 ipg, u32 magic, u32 gpw, u32 lcap, u32 leave, PrepOut po) {  // 8 wavefronts per SIMD: the kernel is bound by requests in flight (r04: 106 SGPRs had left 7)
   __shared__ u16 q_ent[FUSED_QCAP];  // lane | operation << 8
+  __shared__ u8 q_keep[256], q_rem[256];  // a lane's surviving operations (for a second pass over more than one round of them) and those not yet queued
   __shared__ u32 q_n, c_probe, l_n, s_total, s_base;
   __shared__ u32 g_cnt[16], g_start[16], g_alive[16], g_base[16];
   __shared__ unsigned long long g_occ[16];   // TAKE: occurrences of a group's kept strings, each clamped to max_locations
@@ -740,14 +751,59 @@ __global__ void __launch_bounds__(256, 8) k_search1s(FmView f, Batch b, SearchOu
       }
     }
   }
+  if (leave & 4u) mask_all = 0;  // DICEY_EXP=2: the probe phase alone (no survivor is followed up)
+  // The survivors' second look (head_window_occurs), by the lane that holds the candidate: the FIRST K2 characters of a string longer
+  // than K2 must occur as well.  Two of three tail-window survivors end here, so they never enter the queue.  Same shape as above:
+  // operations unrolled (cand1 folds), addresses, then the loads, then the tests; a lane asks only about its survivors.  In halves
+  // of four operations, and with the group's record read again (a line the lane has just had) instead of kept across the eight
+  // loads above: either one more live value there costs the eighth wavefront per SIMD its 64 registers.
+  if (K2 && mask_all) {  // (a lane with a survivor has a query and a position)
+    u32 tid = threadIdx.x;
+    asm volatile("" : "+v"(tid) : : "memory");
+    const u32 lg = (tid * magic) >> 16, pos = tid - lg * ipg + 1;
+    const uint4 raw = ginfo_of(lg, g_first + lg);
+    const u64 qpk = (u64)raw.y << 32 | raw.x;
+    const u32 m = raw.z, R = m - pos;
+    const u32 longer = INDEL ? ((u32)(m - 1 > K2) | (m > K2 ? 14u : 0u) | (m + 1 > K2 ? 240u : 0u)) : (m > K2 ? 15u : 0u);
+    const u32 need = mask_all & longer;
+    nprobe += (u32)__popc(need);
+    if (need && !(leave & 2u)) {  // (leave bit 1: DICEY_EXP=1, every head probe passes)
+      const u64 mask2 = (1ULL << (2 * K2)) - 1;
+#pragma unroll
+      for (u32 h0 = 0; h0 < NOPS; h0 += 4) {
+        const u32* haddr[4];
+        u32 hbit[4], hword[4];
+        // one copy of the filter per length: the deletion's (Hamming: the string's own) and the substitutions', then the insertions'
+        auto copy_of = [&](const u32 mlen) {
+          const u32 cut = mlen > K2 ? mlen - K2 : 0u, t = R > cut ? R - cut : 0u;
+          return kf_copy(f.kf2, t < K2 ? t : K2 - 1);
+        };
+        const KfCopy c0 = copy_of(h0 ? m + 1 : INDEL ? m - 1 : m), c1 = (INDEL && !h0) ? copy_of(m) : c0;
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+          u64 s_pk;
+          u32 mlen, ow;
+          (void)cand1<INDEL>(qpk, m, pos, h0 + k, s_pk, mlen, ow);
+          const u32 cut = mlen > K2 ? mlen - K2 : 0u;
+          haddr[k] = kf_word(k ? c1 : c0, (s_pk >> (2 * cut)) & mask2, hbit[k]);
+        }
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) hword[k] = ((need >> (h0 + k)) & 1u) ? *haddr[k] : 0xFFFFFFFFu;
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) mask_all &= ~((~(hword[k] >> hbit[k]) & 1u) << (h0 + k));
+      }
+    }
+  }
+  // (the head probes are counted with the tail probes, in front of the queue's barrier: wavefronts that end there have contributed)
   nprobe = wave_sum32(nprobe);
   if (lane == 0 && nprobe) atomicAdd(&c_probe, nprobe);
   const u32 shard = blockIdx.x & (NSHARD - 1);
-  u32 steps = 0, nlook = 0, nhead = 0;
+  u32 steps = 0, nlook = 0;
   // the dense phase over the queue's first qn entries: survivors rebuilt, table entry, extension; occurring strings to the LDS list
   // (to_lds) or, for a workgroup whose list overflowed, to the generic leaf buffer exactly like k_search1p
-  auto dense = [&](const bool to_lds, const u32 qn) {
-    for (u32 e0 = 0; e0 < qn; e0 += 256) {
+  // (every entry has passed both windows already: no probe here.  `stride` = lanes of the workgroup that are still resident)
+  auto dense = [&](const bool to_lds, const u32 qn, const u32 stride) {
+    for (u32 e0 = 0; e0 < qn; e0 += stride) {
       if (e0 + (threadIdx.x & ~63u) >= qn) break;
       const u32 e = e0 + threadIdx.x;
       if (e < qn) {
@@ -758,15 +814,10 @@ __global__ void __launch_bounds__(256, 8) k_search1s(FmView f, Batch b, SearchOu
         u64 s_pk;
         u32 mlen, ow;
         (void)cand1<INDEL>((u64)raw.y << 32 | raw.x, raw.z, pos, op, s_pk, mlen, ow);
-        u32 lo = 0, hi = 0, pre_first = 0xFFFFFFFFu;
-        if (to_lds) nhead += (K2 && mlen > K2);
-        if ((leave & 2u) || head_window_occurs(f, s_pk, mlen, raw.z - pos)) {  // (leave bit 1: DICEY_EXP=1, no head probe)
-          const KtabEntry iv = ktab_entry(f, s_pk & kmask);
-          if (to_lds) ++nlook;
-          lo = iv.lo;
-          hi = iv.hi;
-          pre_first = iv.pre_first;
-        }
+        const KtabEntry iv = ktab_entry(f, s_pk & kmask);
+        if (to_lds) ++nlook;
+        u32 lo = iv.lo, hi = iv.hi;
+        const u32 pre_first = iv.pre_first;
         u64 rs = s_pk >> (2 * K);
         u32 n = mlen - K;
         // r04: a narrow table interval (<= 16 suffixes, the usual case on a genome without repeats) is not extended character by
@@ -837,10 +888,15 @@ __global__ void __launch_bounds__(256, 8) k_search1s(FmView f, Batch b, SearchOu
       }
     }
   };
-  // survivors enter the queue in rounds of at most FUSED_QCAP; `gone`: this wavefront ended behind the probe phase
+  // survivors enter the queue in rounds of at most FUSED_QCAP; `gone`: this wavefront ended behind the probe phase.
+  // The leave rule (single round only): a wavefront without a queue entry ends behind the queue's barrier; with at most `tleave`
+  // entries the wavefronts 1-3 end behind their share of the dense phase as well and the first one selects alone.  `nres`: the
+  // lanes that stay (a wavefront that has ended no longer counts at a barrier).
+  const u32 tleave = (leave & 24u) ? (FUSED_QCAP / 8) << ((leave >> 3) & 3u) : FUSED_TLEAVE;  // (DICEY_EXP=4 / 8 / 12: 128 / 256 / 512, the bound's measurement)
+  u32 nres = 256;
   bool gone = false, single_round = false;
   auto rounds = [&](const bool to_lds, const bool may_leave) {
-    u32 rem = mask_all;
+    u32 rem = to_lds ? mask_all : (u32)q_keep[threadIdx.x];
     for (u32 round = 0;; ++round) {
       while (rem) {
         const u32 op = (u32)__ffs((int)rem) - 1u;
@@ -854,34 +910,44 @@ __global__ void __launch_bounds__(256, 8) k_search1s(FmView f, Batch b, SearchOu
       if (round == 0) {
         if (to_lds && threadIdx.x == 0 && c_probe) atomicAdd(&o.ctr->probes[shard], (unsigned long long)c_probe);
         single_round = raw_n <= FUSED_QCAP;
-        // one wavefront's worth of survivors and nothing left over: the other wavefronts end here, their slots go to the next workgroup
-        if (may_leave && raw_n <= 64 && threadIdx.x >= 64) {
+        if (to_lds && !single_round) q_keep[threadIdx.x] = (u8)mask_all;  // for the hand-over of a list that overflows
+        // wavefronts without an entry end here, their slots go to the next workgroup (the first one stays for the select stage)
+        if (may_leave && single_round && threadIdx.x >= 64 && (threadIdx.x & ~63u) >= raw_n) {
           gone = true;
           return;
         }
       }
-      dense(to_lds, qn);
+      if (raw_n > FUSED_QCAP) q_rem[threadIdx.x] = (u8)rem;  // (more rounds, the rare case: nothing of the survivor mask stays in a register across the dense phase)
+      dense(to_lds, qn, 256);
       if (raw_n <= FUSED_QCAP) return;
       __syncthreads();
       if (threadIdx.x == 0) q_n = 0;
       __syncthreads();
+      rem = q_rem[threadIdx.x];
     }
   };
-  if (leave & 4u) mask_all = 0;  // DICEY_EXP=2: the probe phase alone (no survivor is followed up)
   rounds(true, (leave & 1u) != 0);
   if (gone) return;
   steps = wave_sum32(steps);
   nlook = wave_sum32(nlook);
-  nhead = wave_sum32(nhead);
   if (lane == 0) {
     if (steps) atomicAdd(&o.ctr->steps[shard], (unsigned long long)steps);
     if (nlook) atomicAdd(&o.ctr->lookups[shard], (unsigned long long)nlook);
-    if (nhead) atomicAdd(&o.ctr->probes[shard], (unsigned long long)nhead);
+  }
+  if ((leave & 1u) && single_round) {  // (q_n is still the single round's count)
+    const u32 raw_n = q_n;
+    if (raw_n <= tleave) {  // the list is short: what is left belongs to the first wavefront
+      if (threadIdx.x >= 64) {
+        __threadfence_block();  // this wavefront's list entries are in LDS before it stops counting at the barrier
+        return;
+      }
+      nres = 64;
+    } else nres = raw_n >= 256 ? 256u : (raw_n + 63u) & ~63u;
   }
   __syncthreads();
   const u32 nl = l_n;
   if (nl > lcap) {  // this workgroup's groups take the generic path (selbase stays "generic")
-    if (single_round) dense(false, q_n < FUSED_QCAP ? q_n : FUSED_QCAP);  // the queue still holds every survivor
+    if (single_round) dense(false, q_n < FUSED_QCAP ? q_n : FUSED_QCAP, nres);  // the queue still holds every survivor
     else {
       __syncthreads();
       if (threadIdx.x == 0) q_n = 0;
@@ -892,8 +958,9 @@ __global__ void __launch_bounds__(256, 8) k_search1s(FmView f, Batch b, SearchOu
   }
   // ---- select, per group, in LDS.  Up to 64 strings (the usual workgroup: 12 groups of two or three): by the first wavefront
   // alone.  More strings (repeat families: hundreds per workgroup): all four wavefronts share the pair loops (one wavefront alone
-  // took 0.74 instead of 0.51 ms per step on the repeats genome).
-  const u32 sstep = nl <= 64 ? 64u : 256u;
+  // took 0.74 instead of 0.51 ms per step on the repeats genome) — all that are still here: a queue of more than `tleave` entries
+  // has kept every wavefront that had one.  The loops stride by sstep, so any number of wavefronts gives the same result.
+  const u32 sstep = nl <= 64 ? 64u : nres;
   if (threadIdx.x >= sstep) return;
   for (u32 i = threadIdx.x; i < nl; i += sstep) l_pos[i] = (u16)atomicAdd(&g_cnt[(l_meta[i] >> 6) & 15u], 1u);
   __syncthreads();
