@@ -239,14 +239,21 @@ class FmIndex:
         return [out[off[i]:off[i + 1]].copy() for i in range(len(recs))]
 
     def query_mappability(self, seqs: Sequence, k: int = 100, forward_only: bool = False, max_count: int = 0, mismatches: int = 0,
-                          stats: Optional[dict] = None, anchor: Optional[int] = None):
+                          stats: Optional[dict] = None, anchor: Optional[int] = None, iupac: bool = False, max_degeneracy: int = 0):
         """k-mer counts for sequences that are NOT in the index (include/dicey_gpu.h dg_query_map): a list with one numpy uint32 array
         per record, value[p] = the number of windows of the genome within Hamming distance `mismatches` (0..2) of the k-mer w at p of the
         record, plus those within it of revcomp(w) (w alone with forward_only); 0 = absent from the genome; QMAP_INVALID where p + k runs
         past the record or w holds a byte other than A/C/G/T; min(value, max_count) when max_count > 0.  str records are upper-cased,
         bytes go through as given.  `stats`, when given, receives dg_qmap_stats_t.  With `anchor` = a (0..k; dg_query_map_anchored) only
         windows that match the LAST a bases of w, the oligo's 3' end, exactly are counted; on the other strand these are the first a
-        bases of the window.  None calls dg_query_map."""
+        bases of the window.  None calls dg_query_map.  With `iupac` (dg_query_map_iupac, k at most 64) the records may hold the IUPAC
+        codes R Y S W K M B D H V N, each a set of bases: a window's mismatches are its letters outside the sets, the anchored letters
+        must lie inside theirs, and every window counts once however many expansions of w it is close to; k-mers with more than
+        `max_degeneracy` expansions (1..4096, 0 = 256) are QMAP_INVALID and counted in stats["too_degenerate"].  `stats` then receives
+        dg_qmap_iupac_stats_t."""
+        if iupac:
+            prm = _capi.QmapIupacParams(k, mismatches, anchor or 0, 1 if forward_only else 0, max_count, max_degeneracy, 0, (C.c_uint32 * 3)(0, 0, 0))
+            return self._query(self._L.dg_query_map_iupac, prm, _capi.QmapIupacStats(), seqs, stats)
         if anchor is None:
             prm = _capi.QmapParams(k, mismatches, 1 if forward_only else 0, max_count, 0, (C.c_uint32 * 3)(0, 0, 0))
             return self._query(self._L.dg_query_map, prm, _capi.QmapStats(), seqs, stats)

@@ -118,6 +118,18 @@ class QmapAnchorParams(C.Structure):
                 ("max_count", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class QmapIupacParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("mismatches", C.c_uint32), ("anchor", C.c_uint32), ("forward_only", C.c_int32),
+                ("max_count", C.c_uint32), ("max_degeneracy", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class QmapIupacStats(C.Structure):
+    _fields_ = [("positions", C.c_uint64), ("valid", C.c_uint64), ("steps", C.c_uint64), ("table_reads", C.c_uint64),
+                ("verified_rows", C.c_uint64), ("early_exits", C.c_uint64), ("launches", C.c_uint64), ("too_degenerate", C.c_uint64),
+                ("degenerate", C.c_uint64), ("expansions", C.c_uint64), ("ms_valid", C.c_double), ("ms_search", C.c_double),
+                ("ms_total", C.c_double)]
+
+
 class QminlenParams(C.Structure):
     _fields_ = [("min_k", C.c_uint32), ("max_k", C.c_uint32), ("mismatches", C.c_uint32), ("forward_only", C.c_int32),
                 ("at_most", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
@@ -160,7 +172,7 @@ SYMBOLS = ["dg_index_open", "dg_index_close", "dg_index_stats", "dg_count", "dg_
            "dg_chit_unpack", "dg_normalize_query", "dg_hunt_expand", "dg_index_stream", "dg_fm9_check",
            "dg_mappability", "dg_map_values", "dg_map_runs", "dg_map_device_values", "dg_map_stats", "dg_map_free",
            "dg_mappability_mm", "dg_map_mm_stats", "dg_min_unique", "dg_query_map", "dg_query_min_len",
-           "dg_query_map_anchored", "dg_query_min_len_end"]
+           "dg_query_map_anchored", "dg_query_min_len_end", "dg_query_map_iupac"]
 
 _lib = None
 
@@ -241,6 +253,7 @@ def load(path=None):
     L.dg_query_min_len.argtypes = [vp, C.POINTER(QminlenParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QminlenStats)]
     L.dg_query_map_anchored.argtypes = [vp, C.POINTER(QmapAnchorParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapStats)]
     L.dg_query_min_len_end.argtypes = [vp, C.POINTER(QminlenEndParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QminlenStats)]
+    L.dg_query_map_iupac.argtypes = [vp, C.POINTER(QmapIupacParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapIupacStats)]
     L.dg_map_free.restype = None
     if path is None:
         _lib = L

@@ -7,6 +7,7 @@
 // With -q -l the value is the query minimum length (dg_query_min_len): the shortest k-mer from the position with at most -t places in the genome.
 // With -q -a the last -a bases of every k-mer, the oligo's 3' end, must match exactly (dg_query_map_anchored).
 // With -q -l -E the length is that of the shortest specific k-mer that ENDS at the position, its last -a bases exact (dg_query_min_len_end).
+// With -q -I the records may hold IUPAC codes, each letter a set of bases (dg_query_map_iupac).
 #include <zlib.h>
 
 #include <algorithm>
@@ -27,7 +28,7 @@ const OptSpec kMapOpts[] = {{"help", '?', false},  {"genome", 'g', true},  {"kme
                             {"mismatches", 'e', true}, {"minunique", 'u', false},
                             {"query", 'q', true}, {"minlength", 'l', false}, {"shortest", 's', true},
                             {"atmost", 't', true}, {"anchor", 'a', true},
-                            {"byend", 'E', false}};
+                            {"byend", 'E', false}, {"iupac", 'I', false}, {"maxdegeneracy", 'D', true}};
 
 void map_usage() {
   std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz [-q targets.fa.gz]" << std::endl;
@@ -45,6 +46,8 @@ void map_usage() {
                "  -t [ --atmost ] arg (=0)           with -l: a length is specific when its k-mer has at most this many places in the genome\n"
                "  -a [ --anchor ] arg                with -q: the last arg bases of every k-mer must match exactly (0..-k)\n"
                "  -E [ --byend ]                     with -l: the length of the shortest specific k-mer that ENDS at the position; -a then 0..-s\n"
+               "  -I [ --iupac ]                     with -q: the records may hold IUPAC codes (R Y S W K M B D H V N), each a set of bases; -k 10..64\n"
+               "  -D [ --maxdegeneracy ] arg (=256)  with -I: k-mers with more expansions than this have no line (1..4096)\n"
                "  -o [ --outfile ] arg               gzipped output file (default: plain text on stdout)\n"
                "\n"
                "Output: bedGraph lines name, start, end, value (0-based, end exclusive) of maximal runs of equal values, where the value\n"
@@ -74,6 +77,11 @@ void map_usage() {
                "bases exactly are counted; the 3' end stays where it is while the oligo grows at its 5' end, so a longer oligo never has more\n"
                "places.  The lines are at the coordinates of the oligo's LAST base; positions without such a length, and positions where not\n"
                "even a k-mer of length -s ends, have no line.\n"
+               "With -q -I a letter of a record may be an IUPAC code, which stands for a set of bases (R = A or G, ... N = any): a degenerate primer,\n"
+               "or a probe with an N at a SNP site.  A k-mer of the genome mismatches where its base lies outside the record's set, the last -a\n"
+               "letters must hold the genome's bases, and every k-mer of the genome counts once however many expansions of the record's k-mer it\n"
+               "is close to.  Positions whose k-mer has more than -D expansions have no line; their number is reported on stderr.  -I cannot be\n"
+               "combined with -l, -u or -E, and -k is at most 64 then.\n"
                "\n";
 }
 
@@ -133,9 +141,9 @@ bool read_fasta(const std::string& path, std::vector<std::string>& names, std::v
 
 // bedGraph of the query records: one line per maximal run of equal values over valid positions, zero included.  With lp (-l) the values
 // are minimum lengths and zero, no length, has no line either, and with ep (-l -E) those by end position, at the coordinates of the
-// k-mer's last base; with ap (-a) they are the anchored counts
+// k-mer's last base; with ap (-a) they are the anchored counts, with ip (-I) those of records with IUPAC codes
 int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_params* lp, const dg_qminlen_end_params* ep,
-                    const dg_qmap_anchor_params* ap, const std::string& query, const std::string& outfile) {
+                    const dg_qmap_anchor_params* ap, const dg_qmap_iupac_params* ip, const std::string& query, const std::string& outfile) {
   std::vector<std::string> names, seqs;
   if (!read_fasta(query, names, seqs)) return bail("Error: Could not read any sequence from " + query + "!");
   std::vector<uint64_t> off(seqs.size() + 1, 0);
@@ -144,11 +152,16 @@ int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_par
   all.reserve(off.back());
   for (const std::string& s : seqs) all += s;
   std::vector<uint32_t> val(off.back());
-  const int rc = ep   ? dg_query_min_len_end(ix, ep, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
+  dg_qmap_iupac_stats_t ist{};
+  const int rc = ip   ? dg_query_map_iupac(ix, ip, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), &ist)
+                 : ep ? dg_query_min_len_end(ix, ep, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
                  : lp ? dg_query_min_len(ix, lp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
                  : ap ? dg_query_map_anchored(ix, ap, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr)
                       : dg_query_map(ix, &qp, (const uint8_t*)all.data(), off.data(), seqs.size(), val.data(), nullptr);
   if (rc != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
+  if (ist.too_degenerate)
+    std::cerr << "Warning: " << ist.too_degenerate << " positions have a k-mer with more than " << (ip->max_degeneracy ? ip->max_degeneracy : 256u)
+              << " expansions (-D) and no line!" << std::endl;
   FILE* fo = stdout;
   if (!outfile.empty()) {
     fo = std::fopen(outfile.c_str(), "wb");
@@ -226,8 +239,8 @@ int mappability_main(int argc, char** argv) {
   }
   std::string genome, outfile, query;
   bool help = false, have_genome = false, forward = false, minunique = false, have_query = false, minlength = false, have_shortest = false,
-       have_atmost = false, have_anchor = false, byend = false;
-  long long k = 100, maxcount = 0, mismatches = 0, shortest = 10, atmost = 0, anchor = 0;
+       have_atmost = false, have_anchor = false, byend = false, iupac = false, have_maxdeg = false;
+  long long k = 100, maxcount = 0, mismatches = 0, shortest = 10, atmost = 0, anchor = 0, maxdeg = 256;
   for (auto& kv : p.kv) {
     if (kv.first == "help") help = true;
     else if (kv.first == "genome") { genome = kv.second; have_genome = true; }
@@ -243,6 +256,8 @@ int mappability_main(int argc, char** argv) {
     else if (kv.first == "atmost") { atmost = std::strtoll(kv.second.c_str(), nullptr, 10); have_atmost = true; }
     else if (kv.first == "anchor") { anchor = std::strtoll(kv.second.c_str(), nullptr, 10); have_anchor = true; }
     else if (kv.first == "byend") byend = true;
+    else if (kv.first == "iupac") iupac = true;
+    else if (kv.first == "maxdegeneracy") { maxdeg = std::strtoll(kv.second.c_str(), nullptr, 10); have_maxdeg = true; }
   }
   if (help || !have_genome || !p.positional.empty()) {
     map_usage();
@@ -262,6 +277,13 @@ int mappability_main(int argc, char** argv) {
   if (have_anchor && !have_query) return bail("Error: --anchor needs --query!");
   if (have_anchor && minlength && !byend) return bail("Error: --anchor cannot be combined with --minlength!");
   if (have_anchor && (anchor < 0 || anchor > k)) return bail("Error: anchor " + std::to_string(anchor) + " outside 0.." + std::to_string(k) + " (-k)!");
+  if (iupac && !have_query) return bail("Error: --iupac needs --query!");
+  if (iupac && minunique) return bail("Error: --iupac cannot be combined with --minunique!");
+  if (iupac && minlength) return bail("Error: --iupac cannot be combined with --minlength!");
+  if (iupac && byend) return bail("Error: --iupac cannot be combined with --byend!");
+  if (have_maxdeg && !iupac) return bail("Error: --maxdegeneracy needs --iupac!");
+  if (iupac && k > 64) return bail("Error: k-mer length " + std::to_string(k) + " outside 10..64 (--iupac)!");
+  if (maxdeg < 1 || maxdeg > 4096) return bail("Error: maxdegeneracy " + std::to_string(maxdeg) + " outside 1..4096!");
   if (!file_nonempty(genome)) return bail("Error: Genome does not exist!");
   if (have_query && !file_nonempty(query)) return bail("Error: Query file " + query + " does not exist or is empty!");
   if (byend && !minlength) return bail("Error: --byend needs --minlength!");
@@ -293,7 +315,10 @@ int mappability_main(int argc, char** argv) {
     const dg_qmap_anchor_params ap = {(uint32_t)k, (uint32_t)mismatches, (uint32_t)anchor, forward ? 1 : 0, (uint32_t)maxcount, 0u, {0u, 0u}};
     const dg_qminlen_end_params ep = {(uint32_t)shortest, (uint32_t)k, (uint32_t)mismatches, (uint32_t)anchor, forward ? 1 : 0, (uint32_t)atmost, 0u,
                                       {0u, 0u}};
-    return write_query_map(ix, qp, minlength && !byend ? &lp : nullptr, byend ? &ep : nullptr, have_anchor && !byend ? &ap : nullptr, query, outfile);
+    const dg_qmap_iupac_params ip = {(uint32_t)k, (uint32_t)mismatches, (uint32_t)anchor, forward ? 1 : 0, (uint32_t)maxcount, (uint32_t)maxdeg, 0u,
+                                     {0u, 0u, 0u}};
+    return write_query_map(ix, qp, minlength && !byend ? &lp : nullptr, byend ? &ep : nullptr, have_anchor && !byend && !iupac ? &ap : nullptr,
+                           iupac ? &ip : nullptr, query, outfile);
   }
   dg_map_mm_params mp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, 0u};
   dg_min_unique_params up = {(uint32_t)k, forward ? 1 : 0, 0u, 0u};

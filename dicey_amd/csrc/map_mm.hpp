@@ -17,6 +17,10 @@
 // `if constexpr`: on an MmLane the front end then drops it before anything is inlined.  A helper that merely returns false there is folded
 // later and moves blocks of the e >= 1 kernels (DESIGN.md §10 has the instruction counts).  The kernels set the lane up with mm_lane_init
 // and mm_set_strand and flush it with mm_flush; the strand loop itself stays in each kernel (§10 again).
+// Degenerate (dg_query_map_iupac, query_iupac.hpp): the same search on a SetLane, whose k-mer w holds IUPAC codes.  The lane follows one
+// concrete expansion v of w at a time, and the letters a substitution may NOT take at a pattern index are a 4-bit mask (mm_barred): the
+// other members of the code's set always, every letter where v does not show the set's lowest member or the index is anchored.  Each
+// window is then reached from exactly one expansion.  Lane::sets is a compile-time trait written like Lane::anchored.
 #pragma once
 #include "text_bits.hpp"
 
@@ -27,7 +31,7 @@ struct MmCounters {  // device record, one wave_add per field and wavefront
 };
 
 struct MmLane {  // one lane's search of one k-mer w: its constants and the running results
-  static constexpr bool anchored = false;
+  static constexpr bool anchored = false, sets = false;
   const u8* pat;  // the buffer w is read from: the text for a group head, the query buffer for k_qmap (query_map.hpp).  8-byte reads of
                   // it touch only the aligned words that overlap [p, p + k + 8): never in front of an 8-aligned buffer, and behind its
                   // last k-mer inside the text's slack.  Windows are always read from f.text
@@ -44,6 +48,50 @@ struct AnchLane : MmLane {  // and the steps of the current strand at which the 
   static constexpr bool anchored = true;
   u32 t0, t1;
 };
+
+// and w may hold IUPAC codes (k <= 64): the lane searches the expansion v of w that `sel` names.  All masks are over the indices of the
+// CURRENT strand's pattern (bit i = pattern[i]; revcomp(w)[i] is w[k-1-i] with its set complemented)
+struct SetLane : MmLane {
+  static constexpr bool anchored = false, sets = true;
+  u64 deg;         // the pattern's degenerate indices
+  u64 sel0, sel1;  // bit planes of the member v shows there: 0 = the set's lowest code, the canonical member
+  u64 allow;       // indices at which a letter outside the set may be substituted: not anchored, and v shows the canonical member
+};
+
+// the 4-bit set of an IUPAC letter over the codes of acgt_code (bit 0 = A, 1 = C, 2 = G, 3 = T); 0 for every other byte, U and lower
+// case included.  The letters 'A'..'Y' are two words of nibbles
+DG_DEV u32 iupac_set(u32 b) {
+  constexpr u64 lo = 0x1ULL | 0xEULL << 4 | 0x2ULL << 8 | 0xDULL << 12 | 0x4ULL << 24 | 0xBULL << 28 | 0xCULL << 40 | 0x3ULL << 48 | 0xFULL << 52;
+  constexpr u64 hi = 0x5ULL << 4 | 0x6ULL << 8 | 0x8ULL << 12 | 0x7ULL << 20 | 0x9ULL << 24 | 0xAULL << 32;  // from 'Q' on
+  const u32 x = b - 'A';
+  if (x > 24u) return 0;
+  return (u32)((x < 16u ? lo >> (4 * x) : hi >> (4 * (x - 16u))) & 15u);
+}
+
+// the set at pattern index i of the lane's current strand, and the code v shows there
+DG_DEV u32 mm_set_at(const SetLane& c, u32 i, u32& pc) {
+  u32 S = iupac_set(c.pat[c.rev ? c.p + c.k - 1 - i : c.p + i]);
+  if (c.rev) S = __brev(S) >> 28;  // the complement of code x is 3 - x
+  u32 m = S;
+  const u32 idx = (u32)((c.sel0 >> i) & 1ULL) | (u32)((c.sel1 >> i) & 1ULL) << 1;
+  if (idx >= 1) m &= m - 1;
+  if (idx >= 2) m &= m - 1;
+  if (idx >= 3) m &= m - 1;
+  pc = (u32)__ffs((int)m) - 1u;
+  return S;
+}
+// the letters no substitution at pattern index i may take, S being the set there
+DG_DEV u32 mm_barred(const SetLane& c, u32 i, u32 S) { return ((c.allow >> i) & 1ULL) ? S : 15u; }
+
+// step t (pattern index k - 1 - t) takes no substitution by letter a (never on a lane without sets; callers write `Lane::sets &&` in front)
+template <class Lane>
+DG_DEV bool mm_step_bars(const Lane& c, u32 t, u32 a) {
+  if constexpr (Lane::sets) {
+    u32 pc;
+    const u32 S = mm_set_at(c, c.k - 1 - t, pc);
+    return (mm_barred(c, c.k - 1 - t, S) >> a) & 1u;
+  } else return false;
+}
 
 // step t is anchored: no substitution there (never on a plain lane; callers write `Lane::anchored &&` in front, see the header)
 template <class Lane>
@@ -67,6 +115,12 @@ DG_DEV u32 mm_pat_code(const FmView& f, const MmLane& c, u32 t) {
   const u32 b = c.pat[c.rev ? c.p + t : c.p + c.k - 1 - t];
   const u32 x = acgt_code(b);
   return c.rev ? 3u - x : x;
+}
+
+DG_DEV u32 mm_pat_code(const FmView& f, const SetLane& c, u32 t) {
+  u32 pc;
+  (void)mm_set_at(c, c.k - 1 - t, pc);
+  return pc;
 }
 
 static constexpr u64 MM_ONES = 0x0101010101010101ULL, MM_LOW7 = 0x7F7F7F7F7F7F7F7FULL, MM_HIGH = 0x8080808080808080ULL;
@@ -93,6 +147,42 @@ DG_DEV u64 mm_pat8(const FmView& f, const MmLane& c, u32 m, u32 j) {
   return mm_complement_bytes(__builtin_bswap64(text8(c.pat, c.p + c.k - m)) >> (8 * (8 - rem)));
 }
 
+// 0x80 in byte b for every bit b of the low eight of x
+DG_DEV u64 mm_bits_to_bytes(u64 x) { return mm_nonzero_bytes(((x & 255ULL) * MM_ONES) & 0x8040201008040201ULL); }
+
+// the degenerate indices among the first n of the word at pattern index j, one bit each (none on a lane without sets)
+template <class Lane>
+DG_DEV u64 mm_set_bytes(const Lane& c, u32 j, u32 n) {
+  if constexpr (Lane::sets) return (c.deg >> j) & (n < 8 ? (1ULL << n) - 1 : 255ULL);
+  else return 0;
+}
+
+// SetLane, the bytes `nz` flags (0x80 each) among the first n of the word at pattern index j, whose text bytes are y; mism counts them all
+// already.  A degenerate index is flagged unless the text shows the very same IUPAC byte, which is no occurrence; where the text shows v's
+// letter it is taken off the count; a text letter inside the set but not v's belongs to another expansion; one outside costs its 1 where
+// mm_barred lets it.  A word without a degenerate index takes the anchored lane's byte masks.  False: the row is rejected
+DG_DEV bool mm_set_word(const SetLane& c, u32 j, u32 n, u64 y, u64 nz, u32& mism, u32 budget) {
+  const u64 deg8 = mm_set_bytes(c, j, n);
+  if (deg8 == 0) {
+    const u64 free8 = mm_bits_to_bytes(c.allow >> j);
+    return mism <= budget && (nz & (~mm_acgt_bytes(y) | ~free8)) == 0;
+  }
+  if (mm_bits_to_bytes(deg8) & ~nz) return false;
+  for (u64 z = nz; z; z &= z - 1) {
+    const u32 b = (u32)__builtin_ctzll(z) >> 3;
+    const u32 Y = iupac_set((u32)(y >> (8 * b)) & 255u);
+    if (__popc(Y) != 1) return false;  // the text shows no A/C/G/T there
+    u32 pc;
+    const u32 S = mm_set_at(c, j + b, pc);
+    if (Y == 1u << pc) {
+      --mism;
+      continue;
+    }
+    if (mm_barred(c, j + b, S) & Y) return false;
+  }
+  return mism <= budget;
+}
+
 // rows [lo, hi) hold the suffixes that start with the t characters consumed so far: count those whose k - t characters in front spell
 // the rest of the pattern with at most `budget` substitutions.  Anchored: a mismatching byte whose pattern index lies in the anchored
 // range [k - t1, k - t0) rejects the row, as a byte outside A/C/G/T does
@@ -114,10 +204,11 @@ DG_DEV void mm_verify(const FmView& f, Lane& c, u32 t, u32 lo, u32 hi, u32 budge
       u64 x = y ^ mm_pat8(f, c, m, j);
       if (m - j < 8) x &= (1ULL << (8 * (m - j))) - 1;
       const u64 nz = mm_nonzero_bytes(x);
-      if (nz) {
+      if (nz || (Lane::sets && mm_set_bytes(c, j, m - j))) {  // (a degenerate index that is not flagged: the text shows the same IUPAC byte)
         mism += (u32)__popcll(nz);
         // (both forms leave the byte masks behind the budget test: they are formed only while the row is still within budget)
-        if constexpr (Lane::anchored) ok = mism <= budget && (nz & (~mm_acgt_bytes(y) | anch_byte_mask(j, i0, i1))) == 0;
+        if constexpr (Lane::sets) ok = mm_set_word(c, j, m - j, y, nz, mism, budget);
+        else if constexpr (Lane::anchored) ok = mism <= budget && (nz & (~mm_acgt_bytes(y) | anch_byte_mask(j, i0, i1))) == 0;
         else ok = mism <= budget && (nz & ~mm_acgt_bytes(y)) == 0;
       }
     }
@@ -150,6 +241,7 @@ DG_DEV void mm_search(const FmView& f, Lane& c, u32 t, u32 lo, u32 hi) {
       if (!(Lane::anchored && mm_fixed_step(c, t))) {
         for (u32 d = 1; d < 4; ++d) {  // the sibling counter of this level
           const u32 a = (pc + d) & 3u;
+          if (Lane::sets && mm_step_bars(c, t, a)) continue;
           const u32 l = sel4(a, nlo[0], nlo[1], nlo[2], nlo[3]), h = sel4(a, nhi[0], nhi[1], nhi[2], nhi[3]);
           if (l < h) mm_search<B - 1>(f, c, t + 1, l, h);
         }
@@ -181,6 +273,7 @@ DG_DEV void mm_strand(const FmView& f, Lane& c) {
     for (u32 i = 0; i < K; ++i) {
       if (Lane::anchored && mm_fixed_step(c, i)) continue;
       for (u64 a = 1; a < 4; ++a) {
+        if (Lane::sets && mm_step_bars(c, i, (u32)((code >> (2 * i)) ^ a) & 3u)) continue;
         if (c.cap && c.total >= c.cap) return;
         const u64 code1 = code ^ (a << (2 * i));
         const KtabEntry e1 = ktab_entry(f, code1);
@@ -190,6 +283,7 @@ DG_DEV void mm_strand(const FmView& f, Lane& c) {
           for (u32 j = 0; j < i; ++j) {
             if (Lane::anchored && mm_fixed_step(c, j)) continue;
             for (u64 b = 1; b < 4; ++b) {
+              if (Lane::sets && mm_step_bars(c, j, (u32)((code >> (2 * j)) ^ b) & 3u)) continue;
               if (c.cap && c.total >= c.cap) return;
               const KtabEntry e2 = ktab_entry(f, code1 ^ (b << (2 * j)));
               ++c.tab;
@@ -214,6 +308,7 @@ DG_DEV void mm_lane_init(Lane& c, const u8* pat, u64 p, u32 k, u32 W, u32 cap) {
   c.total = 0;
   c.steps = c.tab = c.rows = 0;
   if constexpr (Lane::anchored) c.t0 = c.t1 = 0;
+  if constexpr (Lane::sets) c.deg = c.sel0 = c.sel1 = c.allow = 0;
 }
 
 // the lane's next mm_strand is of its k-mer w or, with rev, of revcomp(w).  On an anchored lane the last `anchor` bases of w are exact:

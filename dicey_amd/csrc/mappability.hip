@@ -19,6 +19,7 @@
 // of it: the (k,e) counts of k-mers that are not in the index.  dg_query_min_len (query_min_len.hpp) looks, on the same buffer, for the
 // smallest k at which that count is at most t.  dg_query_map_anchored (query_anchor.hpp) is dg_query_map with the last a bases of every
 // k-mer matched exactly.  dg_query_min_len_end (query_min_len_end.hpp) looks for the smallest k by the oligo's LAST base, anchored.
+// dg_query_map_iupac (query_iupac.hpp) is dg_query_map_anchored for records with IUPAC codes, each letter a set of bases.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -36,6 +37,7 @@
 #include "map_mm.hpp"           // k_heads' sibling for e >= 1 mismatches
 #include "min_unique.hpp"         // the kernels of dg_min_unique
 #include "query_anchor.hpp"       // k_qmap with the k-mer's last bases matched exactly (dg_query_map_anchored)
+#include "query_iupac.hpp"        // k_qmap_anch for k-mers with IUPAC codes, one search per expansion (dg_query_map_iupac)
 #include "query_map.hpp"          // the same search per position of a query buffer (dg_query_map)
 #include "query_min_len.hpp"      // and the search for the smallest specific k per position (dg_query_min_len)
 #include "query_min_len_end.hpp"  // the smallest specific k of the anchored k-mer that ENDS at a position (dg_query_min_len_end)
@@ -458,7 +460,7 @@ static int query_args_check(const char* who, dg_index* ix, const uint8_t* seqs, 
 
 // The device side of a query buffer: the bytes in whole 64-byte blocks with the text's slack behind, one u32 per position, `nbm` bitmaps
 // of nw words each (the A/C/G/T bitmap first, the valid bitmap second) and a counter record.  alloc() checks the free memory and allocates
-// everything; upload() queues the copy and k_acgt_bits.
+// everything; upload() queues the copy and k_acgt_bits or, for records with IUPAC codes, k_iupac_bits.
 struct QueryDev {
   Scratch mem;
   u64 qn = 0, nw_data = 0, nw = 0, q_bytes = 0;
@@ -485,11 +487,12 @@ struct QueryDev {
   }
   u64* acgt() const { return (u64*)bm; }
   u64* valid() const { return acgt() + nw; }
-  int upload(const std::vector<u8>& hq) {
+  int upload(const std::vector<u8>& hq, bool iupac) {
     hipStream_t st = mem.st;
     DG_HIP(hipMemsetAsync((u8*)q + (qn & ~63ULL), 0, q_bytes - (qn & ~63ULL), st));  // the tail of the last block and the slack
     DG_HIP(hipMemcpyAsync(q, hq.data(), qn, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_acgt_bits, dim3(ceil_div(nw, 256)), dim3(256), 0, st, (const u8*)q, qn, acgt(), nw);
+    if (iupac) hipLaunchKernelGGL(k_iupac_bits, dim3(ceil_div(nw, 256)), dim3(256), 0, st, (const u8*)q, qn, acgt(), nw);
+    else hipLaunchKernelGGL(k_acgt_bits, dim3(ceil_div(nw, 256)), dim3(256), 0, st, (const u8*)q, qn, acgt(), nw);
     return DG_OK;
   }
 };
@@ -499,8 +502,10 @@ struct QueryKind {
   u32 nbm;            // bitmaps: 2 when k_valid_bits runs (one k for all positions), 1 when a lane finds its own limit
   u64 chunk;          // default positions per launch
   const char* chunk_env;
+  bool iupac;         // the first bitmap is of the 15 IUPAC letters, not of A/C/G/T alone
 };
-static constexpr QueryKind QUERY_MAP = {2, QMAP_CHUNK, "DICEY_QMAP_CHUNK"}, QUERY_MIN_LEN = {1, QMINLEN_CHUNK, "DICEY_QMINLEN_CHUNK"};
+static constexpr QueryKind QUERY_MAP = {2, QMAP_CHUNK, "DICEY_QMAP_CHUNK", false}, QUERY_MIN_LEN = {1, QMINLEN_CHUNK, "DICEY_QMINLEN_CHUNK", false},
+                           QUERY_MAP_IUPAC = {2, QMAP_CHUNK, "DICEY_QMAP_CHUNK", true};
 
 // The driver of every dg_query_* call.  hq: the records as REC1 '\n' REC2 '\n' ... (qn bytes); vals: u32[qn], one value per buffer
 // position; k: the longest k-mer looked at; label: what the DICEY_TIMING line calls the search.  launch(b, W, p0, p1, grid, block) queues the
@@ -521,7 +526,7 @@ static int query_run(const char* who, dg_index* ix, const QueryKind& kind, u32 k
   const u32 TB = 256;
   DG_HIP(hipMemsetAsync(b.ctr, 0, sizeof(Counters), st));
   DG_HIP(hipEventRecord(tm.ev[0], st));
-  DG_TRY(b.upload(hq));
+  DG_TRY(b.upload(hq, kind.iupac));
   if (kind.nbm > 1) {
     DG_HIP(hipMemsetAsync(b.valid() + b.nw_data, 0, (b.nw - b.nw_data) * 8, st));
     hipLaunchKernelGGL(k_valid_bits, dim3(ceil_div(b.nw_data, TB)), dim3(TB), 0, st, (const u64*)b.acgt(), b.nw_data, k, b.valid());
@@ -583,6 +588,26 @@ static int query_map_impl(const char* who, dg_index* ix, const dg_qmap_params* p
   return DG_OK;
 }
 
+// k_qmap_iupac per chunk of positions: the buffers and chunks of query_map_impl, the valid bitmap over the 15 letters.  max_degeneracy 0: 256
+static int query_map_iupac_impl(const char* who, dg_index* ix, const dg_qmap_iupac_params* prm, const std::vector<u8>& hq, std::vector<u32>& vals,
+                                dg_qmap_iupac_stats_t* stt) {
+  const FmView& f = ix->view;
+  const u32 maxdeg = prm->max_degeneracy ? prm->max_degeneracy : 256u;
+  QiupacCounters hc{};
+  DG_TRY(query_run(who, ix, QUERY_MAP_IUPAC, prm->k, query_label("query map iupac", prm->mismatches, &prm->anchor).c_str(), hq, vals, &hc, stt,
+                   [&](const QueryDev& b, u32 W, u64 p0, u64 p1, dim3 grid, dim3 block) {
+                     with_mismatches(prm->mismatches, [&](auto E) {
+                       hipLaunchKernelGGL(k_qmap_iupac<E.value>, grid, block, 0, b.mem.st, f, (const u8*)b.q, (const u64*)b.valid(), prm->k, prm->anchor,
+                                          maxdeg, prm->forward_only, W, prm->max_count, p0, p1, (u32*)b.out, (QiupacCounters*)b.ctr);
+                     });
+                   }));
+  stt->early_exits = hc.early_exits;
+  stt->too_degenerate = hc.too_degenerate;
+  stt->degenerate = hc.degenerate;
+  stt->expansions = hc.expansions;
+  return DG_OK;
+}
+
 // the same buffer with the A/C/G/T bitmap alone (a lane finds its own limit), k_qminlen per chunk of positions.  anchor: null for
 // dg_query_min_len, else the lengths are by END position with that many last bases exact (k_qminlen_end): the same buffers, chunks and W
 static int query_min_len_impl(const char* who, dg_index* ix, const dg_qminlen_params* prm, const u32* anchor, const std::vector<u8>& hq,
@@ -607,8 +632,8 @@ static int query_min_len_impl(const char* who, dg_index* ix, const dg_qminlen_pa
   return DG_OK;
 }
 
-// What the four dg_query_* entry points do once their parameter block is checked: totals, device, pack, search, unpack, stats.
-// search(hq, vals, &st) is query_map_impl or query_min_len_impl with the caller's name and parameters
+// What the dg_query_* entry points do once their parameter block is checked: totals, device, pack, search, unpack, stats.
+// search(hq, vals, &st) is query_map_impl, query_map_iupac_impl or query_min_len_impl with the caller's name and parameters
 template <class Stats, class Search>
 static int query_call(dg_index* ix, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values, Stats* stats, Search search) {
   const u64 total = (off && nseq) ? off[nseq] : 0;
@@ -707,6 +732,20 @@ int dg_query_map_anchored(dg_index* ix, const dg_qmap_anchor_params* p, const ui
   const dg_qmap_params q = {p->k, p->mismatches, p->forward_only, p->max_count, 0u, {0u, 0u, 0u}};
   return query_call(ix, seqs, off, nseq, values, stats, [&](const std::vector<u8>& hq, std::vector<u32>& vals, dg_qmap_stats_t* st) {
     return query_map_impl("dg_query_map_anchored", ix, &q, &p->anchor, hq, vals, st);
+  });
+}
+
+int dg_query_map_iupac(dg_index* ix, const dg_qmap_iupac_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
+                       dg_qmap_iupac_stats_t* stats) {
+  if (!p) return fail(DG_EINVAL, "dg_query_map_iupac: null argument");
+  if (p->flags || p->reserved[0] || p->reserved[1] || p->reserved[2]) return fail(DG_EINVAL, "dg_query_map_iupac: flags and reserved must be 0");
+  if (p->k < 10 || p->k > 64) return fail(DG_ELIMIT, "dg_query_map_iupac: k = %u outside 10..64", p->k);
+  if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_query_map_iupac: %u mismatches outside 0..2", p->mismatches);
+  if (p->anchor > p->k) return fail(DG_ELIMIT, "dg_query_map_iupac: anchor = %u above k = %u", p->anchor, p->k);
+  if (p->max_degeneracy > 4096) return fail(DG_ELIMIT, "dg_query_map_iupac: max_degeneracy = %u above 4096", p->max_degeneracy);
+  DG_TRY(query_args_check("dg_query_map_iupac", ix, seqs, off, nseq, values, true));
+  return query_call(ix, seqs, off, nseq, values, stats, [&](const std::vector<u8>& hq, std::vector<u32>& vals, dg_qmap_iupac_stats_t* st) {
+    return query_map_iupac_impl("dg_query_map_iupac", ix, p, hq, vals, st);
   });
 }
 

@@ -676,6 +676,54 @@ typedef struct {
 int dg_query_min_len_end(dg_index* ix, const dg_qminlen_end_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
                          dg_qminlen_stats_t* stats /* may be NULL */);
 
+/* ABI 7, additive.  Degenerate query mappability: dg_query_map_anchored for oligos with IUPAC codes, a degenerate primer or a probe with an
+ * N at a SNP site.  The letters of a record are A, C, G, T and R Y S W K M B D H V N, upper case only; U, lower case and every other byte
+ * are invalid exactly as for dg_query_map.  A letter c stands for a set S(c) of bases (R = {A,G}, ... N = all four).  For w = Q[p, p+k) of
+ * these 15 letters:
+ *   deg(w)     = the product of |S(w_j)|,
+ *   dist(u, w) = #{ j : u_j not in S(w_j) } for a window u of the text (windows are dg_query_map's: A/C/G/T only, inside one sequence,
+ *                never starting before position 0; an IUPAC letter IN THE GENOME is never part of an occurrence),
+ *   fwd(p)     = #{valid windows u : dist(u, w) <= e and u_j in S(w_j) for the LAST a indices j},
+ *   rev(p)     = the same against revcomp(w): the complemented sets (R<->Y, K<->M, B<->V, D<->H; S, W, N themselves) in reverse order,
+ *                anchored at the FIRST a indices,
+ *   value(p)   = fwd(p) + rev(p)   (forward_only: fwd(p)); 0 is a value, saturation and max_count as for dg_query_map.
+ * Every window counts ONCE, however many expansions of w it is within e of; a sum of dg_query_map over the expansions counts a window
+ * whose base at a degenerate index lies outside the set several times when e > 0.  value(p) = DG_QMAP_INVALID where no k-mer of the 15
+ * letters starts at p and where deg(w) > max_degeneracy (counted in too_degenerate, not in valid).  On records of A/C/G/T only every
+ * value and the counters valid, steps, table_reads and verified_rows are those of dg_query_map_anchored.  k is 10..64 here: an
+ * expansion's state is a few 64-bit words of registers.  max_degeneracy is 1..4096, 0 = 256.
+ * Checks, in this order: a null block, non-zero flags or reserved DG_EINVAL; k outside 10..64, mismatches > 2, anchor > k or
+ * max_degeneracy > 4096 DG_ELIMIT; off[nseq] + nseq >= 2^31 DG_ELIMIT; no device DG_ENODEV; a null handle, null seqs / off / values
+ * (where there is something to read or write) or decreasing offsets DG_EINVAL; then DG_EINVAL while a dg_hunt_submit batch is in flight
+ * on the handle.  On every failure `values` is left untouched. */
+typedef struct {
+  uint32_t k;              /* k-mer length, 10..64 */
+  uint32_t mismatches;     /* e: 0, 1 or 2 letters of the window outside the k-mer's sets */
+  uint32_t anchor;         /* a: the last a letters of the k-mer take no mismatch, 0..k */
+  int32_t forward_only;    /* non-zero: fwd(p) alone */
+  uint32_t max_count;      /* 0 = exact values, else min(value, max_count) */
+  uint32_t max_degeneracy; /* k-mers with more expansions are not searched; 1..4096, 0 = 256 */
+  uint32_t flags;          /* 0 */
+  uint32_t reserved[3];    /* 0 */
+} dg_qmap_iupac_params;
+typedef struct {
+  uint64_t positions;      /* off[nseq] - off[0]: values written */
+  uint64_t valid;          /* positions with a k-mer of the 15 letters and deg <= max_degeneracy (the others hold DG_QMAP_INVALID) */
+  uint64_t steps;          /* as dg_qmap_stats_t, summed over the expansions */
+  uint64_t table_reads;
+  uint64_t verified_rows;
+  uint64_t early_exits;    /* k-mers whose search stopped at max_count */
+  uint64_t launches;
+  uint64_t too_degenerate; /* positions with a k-mer of the 15 letters and deg > max_degeneracy */
+  uint64_t degenerate;     /* valid positions with deg > 1 */
+  uint64_t expansions;     /* searches started: one per expansion and strand */
+  double ms_valid;
+  double ms_search;
+  double ms_total;         /* ms_valid + ms_search */
+} dg_qmap_iupac_stats_t;
+int dg_query_map_iupac(dg_index* ix, const dg_qmap_iupac_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
+                       dg_qmap_iupac_stats_t* stats /* may be NULL */);
+
 const char* dg_last_error(void);
 int dg_abi_version(void);
 int dg_device_count(void);

@@ -12,6 +12,10 @@ per k, positions/s from the call's wall time and from the device time, the searc
 at e = 0 in the same run, the route a build without dg_query_map offers to the same numbers: dg_count on every k-mer and its reverse
 complement (cut out on the host, uploaded k-fold).  With --query --anchor A[,A..] the same query set goes through
 dg_query_map_anchored (the last A bases of every k-mer matched exactly; `k` stands for the k-mer length) beside dg_query_map at the same k and e.
+With --query --iupac [--degenerate-every N] the same query set goes through dg_query_map_iupac beside dg_query_map (on A/C/G/T records the
+two queue the same search), and then, with a two-fold code that holds the base every N bases, beside the host's scan over expansions at
+e = 0: with m = ceil(k / N) codes at most in a window, 2^m copies of the records (code j shows its member number bit (j mod m) of the copy's
+index) go through dg_query_map and are summed, every window with c codes having met each of its expansions 2^(m-c) times.
 With --query-minlen [--mismatches e] [--atmost t[,t..]] [--mink a --maxk b] [--no-scan] the same query
 set goes through dg_query_min_len (the shortest specific k-mer per position), one warm-up call in front of the timed one: device and wall
 ms, probes per valid position, the longest launch -- and beside it the route a build without it offers: one dg_query_map(k, max_count =
@@ -38,6 +42,9 @@ ap.add_argument("--query", action="store_true", help="time dg_query_map on a 2 M
 ap.add_argument("--query-mb", type=float, default=1.0, help="Mb of each half of the --query set (cut from the genome / random)")
 ap.add_argument("--anchor", default="", help="with --query: time dg_query_map_anchored at these anchors (comma-separated; k = the k-mer length) beside "
                 "dg_query_map at the same k and e (e = 1, 2, or --mismatches when given)")
+ap.add_argument("--iupac", action="store_true", help="with --query: time dg_query_map_iupac beside dg_query_map on the A/C/G/T set, and on the set with a "
+                "two-fold code every --degenerate-every bases beside a scan of dg_query_map over expansions at e = 0 (k at most 64)")
+ap.add_argument("--degenerate-every", type=int, default=16, help="--iupac: bases between two codes of the degenerate set")
 ap.add_argument("--query-minlen", action="store_true", help="time dg_query_min_len (--mink..--maxk, --mismatches, --atmost) beside a per-k scan of dg_query_map")
 ap.add_argument("--by-end", action="store_true", help="--query-minlen: time dg_query_min_len_end (anchors of --anchor, default 0) beside a per-k scan "
                 "of dg_query_map_anchored shifted to the k-mer's last base")
@@ -52,6 +59,8 @@ ap.add_argument("--workdir", default="/dev/shm")
 a = ap.parse_args()
 if a.min_unique and (a.mismatches or a.maxcount):
     ap.error("--min-unique goes with neither --mismatches nor --maxcount")
+if a.iupac and not a.query:
+    ap.error("--iupac goes with --query")
 if a.by_end and not a.query_minlen:
     ap.error("--by-end goes with --query-minlen")
 dev = torch.device("cuda", 0)
@@ -232,6 +241,79 @@ def query_anchor_runs(k, recs):
             print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
 
 
+def query_iupac_runs(k, recs):
+    """dg_query_map and dg_query_map_iupac on the A/C/G/T records, then dg_query_map_iupac on the degenerate set beside the scan over
+    expansions: one warm-up call in front of every timed one"""
+    import numpy as np
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    off = np.zeros(len(recs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(r) for r in recs])
+    offp = off.ctypes.data_as(u64p)
+    INV = _capi.DG_QMAP_INVALID
+
+    def timed(call, prm, st, buf):
+        vals = np.zeros(len(buf), dtype=np.uint32)
+        _capi.check(L, call(ix.handle, C.byref(prm), buf, offp, len(recs), vals.ctypes.data_as(u32p), None))  # (warm-up)
+        t0 = time.time()
+        _capi.check(L, call(ix.handle, C.byref(prm), buf, offp, len(recs), vals.ctypes.data_as(u32p), C.byref(st)))
+        return vals, st, time.time() - t0
+
+    def row(st, wall):
+        v = max(st.valid, 1)
+        return {"valid": st.valid, "wall_ms": round(wall * 1e3, 2), "ms_total": round(st.ms_total, 2), "ms_search": round(st.ms_search, 2),
+                "launches": st.launches, "steps_per_position": round(st.steps / v, 2), "table_reads_per_position": round(st.table_reads / v, 2),
+                "verified_rows_per_position": round(st.verified_rows / v, 2)}
+
+    plain_p = lambda e: _capi.QmapParams(k, e, 0, a.maxcount, 0, (C.c_uint32 * 3)(0, 0, 0))
+    # max_degeneracy 1 on the A/C/G/T set: a k-mer with an N of the genome is invalid there as it is for dg_query_map; the default (256) on
+    # the degenerate set.  A lane walks the expansions of its k-mer one after the other, so the largest degeneracy sets the call's tail
+    iupac_p = lambda e, maxdeg: _capi.QmapIupacParams(k, e, 0, 0, a.maxcount, maxdeg, 0, (C.c_uint32 * 3)(0, 0, 0))
+    buf = b"".join(recs)
+    # the degenerate set: every N-th base, record by record, becomes the two-fold code of itself and `alt`
+    every, m = a.degenerate_every, -(-k // a.degenerate_every)
+    code, alt = np.arange(256, dtype=np.uint8), np.arange(256, dtype=np.uint8)
+    code[list(b"ACGT")], alt[list(b"ACGT")] = list(b"RYKW"), list(b"GTTA")
+    base = np.frombuffer(buf, dtype=np.uint8)
+    at = np.concatenate([int(off[i]) + np.arange(every // 2, len(r), every) for i, r in enumerate(recs)])
+    at = at[np.isin(base[at], np.frombuffer(b"ACGT", dtype=np.uint8))]
+    deg = base.copy()
+    deg[at] = code[base[at]]
+    in_rec = at - off[np.searchsorted(off, at, side="right") - 1].astype(np.int64)
+    number = (in_rec - every // 2) // every  # consecutive codes of a record have consecutive numbers: distinct mod m inside a window
+    ncodes = np.zeros(len(base) + 1, dtype=np.int64)
+    ncodes[1:] = np.cumsum(deg != base)
+    for e in ([a.mismatches] if a.mismatches else [0, 1, 2]):
+        plain, st0, wall0 = timed(L.dg_query_map, plain_p(e), _capi.QmapStats(), buf)
+        runs.append(dict({"query": True, "call": "dg_query_map", "set": "acgt", "k": k, "mismatches": e, "max_count": a.maxcount}, **row(st0, wall0)))
+        print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+        vals, st, wall = timed(L.dg_query_map_iupac, iupac_p(e, 1), _capi.QmapIupacStats(), buf)
+        ok = plain != INV
+        runs.append(dict({"query": True, "call": "dg_query_map_iupac", "set": "acgt", "k": k, "mismatches": e, "max_count": a.maxcount,
+                          "over_dg_query_map": round(st.ms_search / max(st0.ms_search, 1e-9), 3), "same_values": bool((vals == plain).all()),
+                          "same_counters": [st.valid, st.steps, st.table_reads, st.verified_rows] == [st0.valid, st0.steps, st0.table_reads, st0.verified_rows]},
+                         **row(st, wall)))
+        print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+        dvals, dst, dwall = timed(L.dg_query_map_iupac, iupac_p(e, 0), _capi.QmapIupacStats(), deg.tobytes())
+        runs.append(dict({"query": True, "call": "dg_query_map_iupac", "set": "degenerate", "degenerate_every": every, "k": k, "mismatches": e,
+                          "max_count": a.maxcount, "degenerate": dst.degenerate, "too_degenerate": dst.too_degenerate,
+                          "expansions_per_position": round(dst.expansions / max(dst.valid, 1), 2)}, **row(dst, dwall)))
+        if e == 0 and a.maxcount == 0:
+            t0 = time.time()
+            total, ms = np.zeros(len(base), dtype=np.int64), 0.0
+            for c in range(1 << m):
+                copy = base.copy()
+                take = ((c >> (number % m)) & 1).astype(bool)
+                copy[at[take]] = alt[base[at[take]]]
+                v, sc, _ = timed(L.dg_query_map, plain_p(0), _capi.QmapStats(), copy.tobytes())
+                total += np.where(v == INV, 0, v)
+                ms += sc.ms_total
+            win = ncodes[np.minimum(np.arange(len(base)) + k, len(base))] - ncodes[:-1]
+            total >>= np.maximum(m - win, 0)  # a window with c codes met each of its expansions 2^(m-c) times
+            runs[-1].update({"scan_calls": 1 << m, "scan_ms_total": round(ms, 2), "scan_wall_ms": round((time.time() - t0) * 1e3, 2),
+                             "scan_over_call": round(ms / max(dst.ms_total, 1e-9), 2), "same_values": bool((total[ok] == dvals[ok]).all())})
+        print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+
+
 def query_minlen_run(recs, t):
     import numpy as np
     buf = b"".join(recs)
@@ -350,7 +432,9 @@ if a.query_minlen:
 elif a.query:
     recs = query_set()
     for k in [int(x) for x in a.ks.split(",")]:
-        if a.anchor:
+        if a.iupac:
+            query_iupac_runs(k, recs)
+        elif a.anchor:
             query_anchor_runs(k, recs)
         else:
             query_runs(k, recs)
