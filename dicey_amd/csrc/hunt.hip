@@ -436,7 +436,6 @@ struct BlockGuard {  // the block of the speculative fetch, laid out for capn hi
 // queries above MAX_QLEN take the banded long-query verify (k_verify_long); alignment lengths are 16-bit in dg_hit
 static constexpr u32 LONG_QLEN_MAX = 30000;
 static constexpr u32 TB = 256;
-static_assert(EV_COUNT == sizeof(dg_index::ev) / sizeof(hipEvent_t), "one name per event of the handle");
 
 // What is fixed for the batch, and the three limits of the envelope
 static int make_plan(BatchPlan& pl, const dg_switches& sw, const dg_hunt_params* p, u32 nseq, const void* d_qbytes, const void* d_qoff, size_t nq,
@@ -601,6 +600,32 @@ static int cap_stage(dg_index* ix, const BatchPlan& pl, const uint8_t* h_qbytes,
   return DG_OK;
 }
 
+// What the rules of hunt_hints.hpp (start_caps, decide_attempt, review_attempt, settle_hints) need to know of the batch
+static BatchFacts batch_facts(const dg_index* ix, const BatchPlan& pl, const BatchBufs& bf) {
+  const dg_switches& sw = ix->sw;
+  BatchFacts f;
+  f.fast1 = bf.b.fastK != 0;
+  f.fast2 = bf.b.fast2K != 0;
+  f.packed = pl.packed;
+  f.count_mode = pl.group_counts != nullptr;
+  f.hunt = pl.hunt;
+  f.band_verify = pl.band_verify;
+  f.sax = ix->view.sax != nullptr;
+  f.long_ok = ix->view.kf2.nr && ix->view.kf2.k <= 18;  // word offsets inside a copy stay below 2^32
+  f.long_k = ix->view.kf2.k;
+  f.indel = pl.indel;
+  f.nq = pl.nq;
+  f.ngrp = pl.ngrp;
+  f.nxs = bf.nxs;
+  f.no_fuse = sw.no_fuse;
+  f.no_fuse2 = sw.no_fuse2;
+  f.no_long2 = sw.no_long2;
+  f.no_prep_fusion = sw.no_prep_fusion;
+  f.debug_caps = sw.debug_caps;
+  f.debug_caps_value = (u32)std::max(1, std::atoi(sw.debug_caps_s.c_str()));
+  return f;
+}
+
 // The batch's fixed device pointers (the per-attempt ones: reserve_attempt) and which flat kernels it qualifies for
 static void init_batch(dg_index* ix, const BatchPlan& pl, const CapResult& cr, const GrpLayout& gl, BatchBufs& bf) {
   auto& ws = ix->ws;
@@ -654,6 +679,7 @@ static void init_batch(dg_index* ix, const BatchPlan& pl, const CapResult& cr, c
   b.fast2_minlen = 0;
   b.maxlen_bound = maxlen;
   b.total_qbytes = pl.total;
+  bf.facts = batch_facts(ix, pl, bf);
 }
 
 // cumulative sequence starts: kept for the result (seq_start), uploaded when they changed (sequence lengths rarely do between batches)
@@ -671,9 +697,8 @@ static int upload_seq_starts(dg_index* ix, const uint32_t* seqlen, std::vector<u
   return DG_OK;
 }
 
-// The lanes' common record, read when a batch starts and written when it ends (the two functions list the same fields).
-// pull: what the handle's other lanes have learnt since this lane's previous batch, and the base event of the lanes' common timeline
-static void pull_shared_hints(dg_index* ix, u32& base_gen, hipEvent_t& base_ev) {
+// The base event of the lanes' common timeline (dg_hunt_result::t_search_*), taken when a batch starts
+static void timeline_base(dg_index* ix, u32& base_gen, hipEvent_t& base_ev) {
   dg_index::SharedHints* sh = ix->shared_hints.load();
   if (!sh) return;
   std::lock_guard<std::mutex> lk(sh->mu);
@@ -690,32 +715,6 @@ static void pull_shared_hints(dg_index* ix, u32& base_gen, hipEvent_t& base_ev) 
   }
   base_gen = sh->base_gen;
   base_ev = base_gen ? sh->ev_base[base_gen & 1] : nullptr;
-  if (!sh->valid) return;
-  ix->shard_cap_hint = std::max(ix->shard_cap_hint, sh->shard_cap);
-  ix->flat_cap_hint = std::max(ix->flat_cap_hint, sh->flat_cap);
-  ix->hit_cap_hint = std::max(ix->hit_cap_hint, sh->hit_cap);
-  if (sh->fetch_hits) ix->fetch_hits_hint = sh->fetch_hits;  // (the most recent batch's, like the two below)
-  ix->generic_sticky = std::max(ix->generic_sticky, sh->generic_sticky);
-  ix->jobs_sticky = std::max(ix->jobs_sticky, sh->jobs_sticky);
-  ix->generic_hint = ix->generic_sticky > 0;
-  ix->jobs_hint = ix->jobs_sticky > 0;
-  ix->jobs_big_hint = sh->jobs_big;
-  ix->fused_leaves_hint = sh->fused_leaves;
-}
-// push: for the other lanes' next batches
-static void push_shared_hints(dg_index* ix) {
-  dg_index::SharedHints* sh = ix->shared_hints.load();
-  if (!sh) return;
-  std::lock_guard<std::mutex> lk(sh->mu);
-  sh->shard_cap = std::max(sh->shard_cap, ix->shard_cap_hint);
-  sh->flat_cap = std::max(sh->flat_cap, ix->flat_cap_hint);
-  sh->hit_cap = std::max(sh->hit_cap, ix->hit_cap_hint);
-  sh->fetch_hits = ix->fetch_hits_hint;
-  sh->generic_sticky = ix->generic_sticky;
-  sh->jobs_sticky = ix->jobs_sticky;
-  sh->jobs_big = ix->jobs_big_hint;
-  sh->fused_leaves = ix->fused_leaves_hint;
-  sh->valid = true;
 }
 // The flat search kernel's interval on the lanes' common timeline (dg_hunt_result::t_search_*).  The two base events are used in
 // turn and re-recorded under the shared record's mutex: a batch that outlived two generations (cap-prone or very long batches)
@@ -732,53 +731,19 @@ static void search_interval(dg_index* ix, u32 base_gen, hipEvent_t base_ev, dg_h
   }
 }
 
-// The capacities the first attempt starts from: what was enough for the handle's previous batch, or an estimate from the batch's size
-static void start_caps(const dg_index* ix, const BatchPlan& pl, u64 nxs, Attempt& at) {
-  const u64 nq = pl.nq;
-  at.shard_cap = std::max<u32>(ix->shard_cap_hint, (u32)std::max<u64>(64, (16 * nq + nxs / 8) / NSHARD));
-  at.hit_cap = std::max<u64>(ix->hit_cap_hint, 4 * nq + 1024);
-  // slices of the flat Sel region (k_search1s): what the previous batch's fullest slice needed plus a quarter — kept strings are a
-  // third of the leaf estimate above, and k_locate walks every slot of the region
-  at.flat_req = ix->flat_cap_hint ? ix->flat_cap_hint : at.shard_cap;
-  if (ix->sw.debug_caps) {  // tests: start from tiny capacities to exercise the retry path
-    const char* e = ix->sw.debug_caps_s.c_str();
-    at.shard_cap = (u32)std::max(1, std::atoi(e));
-    at.hit_cap = (u64)std::max(1, std::atoi(e));
-    at.flat_req = at.shard_cap;
-  }
+// The lanes' common record of hints (Hints::merge / publish, hunt_hints.hpp): read when a batch starts, written when it ends
+static void merge_shared_hints(dg_index* ix) {
+  dg_index::SharedHints* sh = ix->shared_hints.load();
+  if (!sh) return;
+  std::lock_guard<std::mutex> lk(sh->mu);
+  if (sh->valid) ix->hints.merge(sh->h);
 }
-
-// What an attempt decides before its first launch (Attempt names the fields a stage sets later)
-static void decide_attempt(const dg_index* ix, const BatchPlan& pl, BatchBufs& bf, Attempt& at) {
-  const dg_switches& sw = ix->sw;
-  Batch& b = bf.b;
-  // Distance 1, every string in 128 bits: k_search1s settles the select stage inside the search kernel (flat Sel region of
-  // NSHARD slices).  The generic kernels (k_search for N-containing / long queries, k_explicit, scan, pack, alive, rank) run
-  // when the previous batch of this handle had work for them; a batch that turns out to need them after all is repeated.
-  // DICEY_NO_FUSED_SELECT: the search without the select stage (k_search1p + the generic select kernels) — what batches with
-  // strings above 42 characters take anyway; the GPU tests run every distance-1 case both ways
-  // r04: the same at edit distance 2 (k_search2p<true, .>: one workgroup per group or per query); DICEY_NO_FUSED_SELECT2 keeps the
-  // generic select kernels for that distance only
-  at.fused = (b.fastK || (b.fast2K && !sw.no_fuse2)) && pl.packed && !sw.no_fuse;
-  at.flat_cap = at.fused ? at.flat_req : 0u;
-  at.generic_on = !at.fused || ix->generic_hint || bf.nxs > 0 || at.force_generic;
-  // edit distance 2: the walker (k_search) only serves the groups k_search2p does not take (N in the query, above 30 nt); it is
-  // launched when the previous batch of the handle had such groups — 0.17 ms of the 13 ms step on batches that have none — and
-  // a batch that has some after all is repeated with it, like the generic kernels at distance 1
-  at.walker_on = !(b.fast2K && !ix->generic_hint && !at.force_generic && bf.nxs == 0);
-  // distance 2: the LONG2 body of k_search2p takes queries whose shortest string still asks the long filter; the handle falls back to
-  // the r04 body while its batches hold shorter ones (short2_sticky), and a batch that turns out to hold some is repeated with it
-  at.long2 = b.fast2K && ix->view.kf2.nr && ix->view.kf2.k <= 18 /* word offsets inside a copy stay below 2^32 */ && !ix->short2_sticky && !at.force_short2 && !sw.no_long2;
-  b.fast2_minlen = at.long2 ? ix->view.kf2.k + (pl.indel ? 2u : 0u) : 0u;
-  // the whole batch on the flat distance-1 path: k_search1s settles the `take` values of its own queries (TAKE form);
-  // DICEY_NO_PREP_FUSION keeps k_take a launch of its own (the GPU suite runs both)
-  at.prep_in = at.fused && b.fastK && !at.generic_on && !pl.group_counts && !sw.no_prep_fusion;
-  at.flat_form = b.fastK ? (at.fused ? (at.prep_in ? 3u : 2u) : 1u) : b.fast2K ? (at.fused ? 5u : 4u) + (at.long2 ? 2u : 0u) : 0u;
-  // hits of the job kernels leave with their context characters (FmView::sax) when the kernel that reads the seeds is
-  // k_verify_memo — the only reader that knows the encoding (HitSeed::len, devfm.hpp)
-  at.with_ctx_hits = pl.hunt && pl.band_verify && ix->view.sax;
-  at.keys_on = at.jobs_on = false;
-  at.direct_ctx = 0;
+static void publish_hints(dg_index* ix) {
+  dg_index::SharedHints* sh = ix->shared_hints.load();
+  if (!sh) return;
+  std::lock_guard<std::mutex> lk(sh->mu);
+  ix->hints.publish(sh->h);
+  sh->valid = true;
 }
 
 // (r02's survivor queue in HBM is gone with k_probe1 / k_finish1; the scan kernel's check keeps its argument)
@@ -859,7 +824,7 @@ static int launch_flat1(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBuf
     // per workgroup (repeat-bearing genomes), then 512; a workgroup whose strings do not fit hands its groups to the generic
     // path.  tests: DICEY_FUSED_LCAP lowers the capacity so that ordinary batches exercise that hand-over
     const u32 lcap_env = sw.fused_lcap ? std::max<u32>(1u, std::min<u32>(FUSED_LCAP, sw.fused_lcap)) : 0u;
-    const u32 lcap = lcap_env ? lcap_env : (ix->fused_leaves_hint > 48ull * g1.x ? FUSED_LCAP : FUSED_LCAP / 2);
+    const u32 lcap = lcap_env ? lcap_env : (ix->hints.fused_leaves > 48ull * g1.x ? FUSED_LCAP : FUSED_LCAP / 2);
     const u32 lds1 = fused_lds_bytes(lcap);
     // bit 0: the leave rule of k_search1s — wavefronts without a queue entry end behind the queue's barrier, the others behind the
     // dense phase when the queue is short.  (r04's form, "at most 64 entries", measured 0.2188 ms with and 0.2194 without: the queue
@@ -910,8 +875,8 @@ static int launch_walker(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBu
   // root-level work split (see k_search): only with the table and with at least one edit to place
   // (r05: also beside the flat distance-1 kernel — the walker is only launched when a batch has groups for it, and those are the
   // queries with N that the split turns from one 1 500-read chain per strand into lanes of a handful of reads)
-  // — while the handle's batches hold such strands (nwin_sticky): 29 M lanes that leave at once cost a repeats-genome step 0.15 ms
-  const u32 items = (ix->view.K && pl.dmax_eff >= 1 && (!b.fastK || ix->nwin_sticky)) ? ix->view.K * (pl.indel ? 9u : 4u) + 1u : 1u;
+  // — while the handle's batches hold such strands (Hints::nwin): 29 M lanes that leave at once cost a repeats-genome step 0.15 ms
+  const u32 items = (ix->view.K && pl.dmax_eff >= 1 && (!b.fastK || ix->hints.nwin.on())) ? ix->view.K * (pl.indel ? 9u : 4u) + 1u : 1u;
   // beside a flat kernel the walker serves a few strands of the batch: with the root split its lanes cover a LIST of them
   // (k_walk_list; room for what the previous batch listed plus a quarter — a list that overflows repeats the batch)
   WalkList wl{nullptr, nullptr, 0u};
@@ -921,7 +886,7 @@ static int launch_walker(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBu
   //  tools/fuzz_hunt.py in the full-size layout found a 12-mer ending in N that lost its two exact hits in Hamming mode)
   const bool flat_on = b.fastK || b.fast2K;
   if ((flat_on || b.nrun_min) && ngrp < 0x7FFFFFFFull) {
-    const u64 walk_cap = at.walk_cap = std::max<u64>(at.walk_cap, flat_on ? std::min<u64>(ngrp, (u64)ix->walk_hint + ix->walk_hint / 4 + 4096) : ngrp);
+    const u64 walk_cap = at.walk_cap = walk_list_room(ix->hints, bf.facts, at);
     DG_TRY(ws[WS_WALK].reserve(2 * (walk_cap + 1) * 4));
     wl.gid = ws[WS_WALK].as<u32>();
     wl.count = &ctr->pad_[CW_N_WALK];
@@ -1075,14 +1040,14 @@ static int launch_locate(dg_index* ix, const BatchPlan& pl, Attempt& at, BatchBu
   if (pl.phase_events) DG_HIP(hipEventRecord(ix->ev[EV_HITS_SCANNED], st));
   // strings with many occurrences go to three job lists: up to 256 occurrences for a wavefront each, more for a workgroup each
   // (those that fit the small buffer of k_locate_topk whole, and the rest)
-  at.jobs_on = ix->jobs_hint || at.force_jobs || pl.p->max_locations > TOPK_KMAX;
+  at.jobs_on = jobs_wanted(ix->hints, at, pl.p->max_locations > TOPK_KMAX);
   // repeat-rich strings: up to TOPK_KMAX positions through the block minima, more (hunt -m above 1 024) by radix passes
   const bool topk = ix->view.nlev > 1;
   // A batch with thousands of repeat-rich strings (the previous batch of this handle tells): intervals up to 4 608 entries go
   // to the small-buffer form of k_locate_topk.  (r03 also ran the three job kernels side by side on helper streams: each
   // slowed down by what the others took — 114 / 220 / 228 us alone, 220 / 494 / 268 us together — and the stage gained
   // 0.08 of 0.91 ms; not worth two more streams per handle.)
-  const bool rich = topk && ix->jobs_big_hint >= 2048;
+  const bool rich = topk && ix->hints.jobs_big >= 2048;
   LocJobs lj;
   for (int l = 0; l < 3; ++l) lj.list[l] = ws[WS_JOBS].as<BigJob>() + (u64)l * JOB_SHARDS * bf.job_shard_cap;
   lj.shard_cap = bf.job_shard_cap;
@@ -1248,7 +1213,7 @@ static int queue_fetch(dg_index* ix, const BatchPlan& pl, const BatchBufs& bf, P
 
 // the fetch queued BEHIND the batch's kernels, for as many hits as the handle's previous fetched batch had (plus 3 %)
 static int queue_spec_fetch(dg_index* ix, const BatchPlan& pl, const Attempt& at, const BatchBufs& bf, BlockGuard& spec) {
-  const u64 capn = std::min<u64>(at.hit_cap, ix->fetch_hits_hint);
+  const u64 capn = std::min<u64>(at.hit_cap, ix->hints.fetch_hits);
   if (!spec.pb || spec.capn != capn) {
     if (spec.pb) pinned_pool().put(spec.pb);
     spec.pb = pinned_pool().get(FetchLayout(pl, capn).bytes);
@@ -1290,7 +1255,7 @@ static int fill_result_host(dg_index* ix, const BatchPlan& pl, const std::vector
     R->qnondna = R->qflags + nq;
     R->qseq = hb + L.o_qseq;
   }
-  ix->fetch_hits_hint = nhits + nhits / 32 + 1024;
+  ix->hints.fetch_hits = nhits + nhits / 32 + 1024;
   return DG_OK;
 }
 
@@ -1377,87 +1342,6 @@ static void print_topk_profile(const Summary& hsum) {
 #endif
 }
 
-// Everything an attempt found wanting is put right before the batch is repeated (one repeat usually serves several causes).
-// Returns whether the batch runs again.
-static bool review_attempt(const Summary& hsum, const BatchPlan& pl, Attempt& at, dg_index* ix) {
-  at.nleaf = hsum.nleaf;
-  at.nhits = hsum.nhits;
-  bool again = false;
-  // the generic kernels were left out, and the batch had work for them after all (queries with N, longer than 31 nt, a workgroup
-  // of k_search1s whose strings did not fit its LDS list): once more, with them
-  if (at.fused && !at.generic_on && (hsum.nleaf > 0 || hsum.n_generic > 0)) {
-    ix->generic_hint = true;
-    at.force_generic = true;
-    again = true;
-  }
-  if (!at.walker_on && hsum.n_generic > 0) {  // edit distance 2: groups for the walker after all
-    ix->generic_hint = true;
-    ix->generic_sticky = 8;
-    at.force_generic = true;
-    again = true;
-  }
-  if (at.long2 && hsum.n_short2 > 0) {  // queries too short for the LONG2 body went to the walker (or to nobody): once more with the r04 body
-    ix->short2_sticky = 8;
-    at.force_short2 = true;
-    again = true;
-  }
-  if (!at.jobs_on && !pl.group_counts && (hsum.jobs_small > 0 || hsum.jobs_big > 0)) {  // strings were queued and nobody served them
-    ix->jobs_hint = true;
-    at.force_jobs = true;
-    again = true;
-  }
-  const u32 worst = (u32)hsum.worst_shard;
-  if (worst > at.shard_cap) {
-    at.shard_cap = worst + worst / 4 + 64;
-    again = true;
-  }
-  if (at.fused && hsum.worst_sel > at.flat_cap) {
-    at.flat_req = (u32)(hsum.worst_sel + hsum.worst_sel / 4 + 64);
-    again = true;
-  }
-  if (!(hsum.overflow & 1) && at.nhits > at.hit_cap) {  // (after a buffer overflow the hit count is not this batch's)
-    at.hit_cap = at.nhits + at.nhits / 4 + 1024;
-    again = true;
-  }
-  if (hsum.overflow & 8u) {  // the walker's group list was too short
-    at.walk_cap = std::min<u64>(pl.ngrp, hsum.n_walk + hsum.n_walk / 4 + 4096);
-    again = true;
-  }
-  ix->walk_hint = (u32)std::min<u64>(hsum.n_walk, 0xFFFFFFFFull);
-  return again;
-}
-
-// What the handle's next batch starts from, after the attempt that stood.
-// The hints are sticky: a kernel family that a batch needed stays on for the next eight batches of the handle, so that a stream
-// that alternates (chunks with and without N-containing queries, with and without repeat-rich strings) does not pay a repeated
-// batch at every change (r03 advice; r04 repeats genome: 4 of 14 rotating steps ran twice).
-static void settle_hints(const Summary& hsum, const BatchPlan& pl, const Attempt& at, const BatchBufs& bf, dg_index* ix) {
-  const Batch& b = bf.b;
-  if (b.fast2K && !at.fused) {
-    if (hsum.n_generic > 0 || bf.nxs > 0) ix->generic_sticky = 8;
-    else if (ix->generic_sticky) --ix->generic_sticky;
-    ix->generic_hint = ix->generic_sticky > 0;
-  }
-  if (at.fused) {
-    if (hsum.nleaf > 0 || hsum.n_generic > 0 || bf.nxs > 0) ix->generic_sticky = 8;
-    else if (ix->generic_sticky) --ix->generic_sticky;
-    ix->generic_hint = ix->generic_sticky > 0;
-  }
-  if (hsum.n_nwin) ix->nwin_sticky = 8;
-  else if (ix->nwin_sticky) --ix->nwin_sticky;
-  if (b.fast2K && !at.long2 && ix->short2_sticky && !at.force_short2) --ix->short2_sticky;  // (eight batches on the r04 body, then LONG2 is tried again)
-  if (!pl.group_counts) {
-    if (hsum.jobs_small > 0 || hsum.jobs_big > 0) ix->jobs_sticky = 8;
-    else if (ix->jobs_sticky) --ix->jobs_sticky;
-    ix->jobs_hint = ix->jobs_sticky > 0;
-  }
-  ix->shard_cap_hint = at.shard_cap;
-  if ((b.fastK || b.fast2K) && hsum.worst_sel) ix->flat_cap_hint = (u32)std::max<unsigned long long>(ix->flat_cap_hint, hsum.worst_sel + hsum.worst_sel / 4 + 64);
-  ix->jobs_big_hint = hsum.jobs_big;
-  if (b.fastK) ix->fused_leaves_hint = hsum.fused_leaves + at.nleaf;
-  ix->hit_cap_hint = std::max<u64>(ix->hit_cap_hint, at.nhits + at.nhits / 4 + 1024);
-}
-
 // One batch through the five kernels.  All sizes that are only known on the device (number of leaves, number of hits)
 // are handled with capacity guesses that the kernels check themselves; the host synchronises ONCE at the end, and
 // repeats the batch with larger buffers in the rare case a capacity was exceeded.
@@ -1468,12 +1352,14 @@ static void settle_hints(const Summary& hsum, const BatchPlan& pl, const Attempt
 //
 // The stages, in order, and the function that runs each:
 //   once per batch   make_plan (limits, what is fixed) -> the fixed workspaces (GrpLayout) -> cap_stage (upload_xs, launch_cap_enum)
-//                    -> init_batch -> upload_seq_starts -> pull_shared_hints -> start_caps
+//                    -> init_batch (batch_facts) -> upload_seq_starts -> timeline_base -> merge_shared_hints -> start_caps
 //   per attempt      decide_attempt -> reserve_attempt -> counters cleared if dirty -> launch_prepare -> launch_search (launch_flat1,
 //                    launch_flat2, launch_walker, launch_nres) -> launch_select -> launch_count, or launch_locate -> launch_verify
 //                    -> k_summary_block -> queue_spec_fetch -> the batch's ONE synchronisation -> review_attempt (again?)
 //   after the last   settle_hints -> fetch_result (fill_result_host) -> fill_result_device -> fill_result_report -> search_interval
-//                    -> push_shared_hints
+//                    -> publish_hints
+// start_caps, decide_attempt, review_attempt and settle_hints are the rules of hunt_hints.hpp: pure functions over the handle's Hints,
+// the batch's facts and the Attempt.
 int run_batch(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uint32_t nseq, const void* d_qbytes,
                      const void* d_qoff, size_t nq, u64 total, u32 maxlen, int fetch, dg_hunt_result** out, SearchExtra* sx,
                      uint64_t* group_counts, const uint8_t* h_qbytes, const uint64_t* h_qoff) {
@@ -1507,15 +1393,17 @@ int run_batch(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uin
 
   u32 base_gen = 0;
   hipEvent_t base_ev = nullptr;
-  pull_shared_hints(ix, base_gen, base_ev);
+  timeline_base(ix, base_gen, base_ev);
+  merge_shared_hints(ix);
   Attempt at;
-  start_caps(ix, plan, bf.nxs, at);
+  start_caps(ix->hints, bf.facts, at);
   BlockGuard spec;
   std::vector<u32> dump_cnt;
   for (int attempt = 0;; ++attempt) {
     if (attempt > 8)
       return fail(DG_ENOMEM, "buffer overflow persists (%llu leaves, %llu hits)", (unsigned long long)at.nleaf, (unsigned long long)at.nhits);
-    decide_attempt(ix, plan, bf, at);
+    decide_attempt(ix->hints, bf.facts, at);
+    bf.b.fast2_minlen = fast2_minlen(bf.facts, at);
     DG_TRY(reserve_attempt(ix, plan, at, bf));
     // counters: left zeroed by the previous batch's last kernel (batch_finish) unless they moved or that batch did not finish;
     // group counters: cleared by k_prepare
@@ -1532,7 +1420,7 @@ int run_batch(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uin
       DG_TRY(launch_verify(ix, plan, at, bf));
     }
     hipLaunchKernelGGL(k_summary_block, dim3(1), dim3(NSHARD), 0, st, bf.ctr, (const u64*)(bf.hit_off + nq), bf.hsum);
-    if (fetch && plan.hunt && ix->fetch_hits_hint) DG_TRY(queue_spec_fetch(ix, plan, at, bf, spec));
+    if (fetch && plan.hunt && ix->hints.fetch_hits) DG_TRY(queue_spec_fetch(ix, plan, at, bf, spec));
     if (host_timing) t_launched = host_us();
     DG_HIP(hipStreamSynchronize(st));  // the only synchronisation of a batch
     DG_HIP(hipGetLastError());
@@ -1547,9 +1435,9 @@ int run_batch(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uin
                   hsum.refused, hsum.refused == 1 ? "y" : "ies", p->max_neighborhood);
     DG_TRY(write_job_dump(ix, bf, dump_cnt));
     print_topk_profile(hsum);
-    if (!review_attempt(hsum, plan, at, ix)) break;
+    if (!review_attempt(hsum, bf.facts, at, ix->hints)) break;
   }
-  settle_hints(hsum, plan, at, bf, ix);
+  settle_hints(hsum, bf.facts, at, ix->hints);
   if (group_counts) {
     DG_HIP(hipMemcpyAsync(group_counts, ws[WS_HITS].p, plan.ngrp * 8, hipMemcpyDeviceToHost, st));
     DG_HIP(hipStreamSynchronize(st));
@@ -1567,7 +1455,7 @@ int run_batch(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uin
   fill_result_device(ix, plan, R);
   fill_result_report(ix, plan, at, bf, cap, R);
   if (base_ev && (bf.b.fastK || bf.b.fast2K)) search_interval(ix, base_gen, base_ev, R);
-  push_shared_hints(ix);
+  publish_hints(ix);
   if (host_timing)
     std::fprintf(stderr, "dicey timing: batch of %zu on stream %p entered at %.0f us: host %.0f us before the synchronisation (last attempt's "
                  "launches included), %.0f us waiting, %.0f us after; device %.3f ms\n", nq, (void*)st, std::fmod(t_enter, 1e8), t_launched - t_enter,
@@ -1606,13 +1494,6 @@ dg_switches dg_switches::read() {
   if (const char* e = exp_env("DICEY_DUMP_JOBS")) w.dump_jobs = e;
   w.exp_bits = (uint32_t)num(exp_env("DICEY_EXP"));  // measurement aid (wrong results): phases of the search / verify kernels switched off
   return w;
-}
-static bool any_lane_busy(dg_index* ix) {
-  if (ix->busy.load()) return true;
-  std::lock_guard<std::mutex> lk(ix->lanes_mu);
-  for (dg_index* l : ix->lanes)
-    if (l && l->busy.load()) return true;
-  return false;
 }
 
 extern "C" {
@@ -1859,7 +1740,7 @@ int dg_hunt(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen, uint3
             const uint64_t* qoff, size_t nq, dg_hunt_result** out) {
   // a submitted batch owns its lane's stream, workspaces and hints until its ticket has been waited for; the blocking call runs on
   // the handle itself and is refused while ANY ticket of the handle is open (dicey_gpu.h)
-  if (ix && any_lane_busy(ix)) return fail(DG_EINVAL, "dg_hunt: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)");
+  if (ix && ix->any_lane_busy()) return fail(DG_EINVAL, "dg_hunt: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)");
   if (ix) ix->sw = dg_switches::read();
   return hunt_host(ix, p, seqlen, nseq, qbytes, qoff, nq, out, nullptr);
 }
@@ -2177,7 +2058,7 @@ int dg_hunt_device(dg_index* ix, const dg_hunt_params* p, const uint32_t* seqlen
   if (!ix || !p || !seqlen || !d_qbytes || !d_qoff || !out) return fail(DG_EINVAL, "dg_hunt_device: null argument");
   *out = nullptr;
   if (!nq) return fail(DG_EINVAL, "dg_hunt_device: empty batch");
-  if (any_lane_busy(ix)) return fail(DG_EINVAL, "dg_hunt_device: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)");
+  if (ix->any_lane_busy()) return fail(DG_EINVAL, "dg_hunt_device: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)");
   ix->sw = dg_switches::read();
   return hunt_device(ix, p, seqlen, nseq, d_qbytes, d_qoff, nq, total_qbytes, fetch, out);
 }

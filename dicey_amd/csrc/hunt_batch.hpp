@@ -1,5 +1,5 @@
-// The data of run_batch (hunt.hip, the only includer): what is fixed for a batch, how its workspaces are carved up, what one attempt
-// decides and what survives a repeat.  The functions that use them are in hunt.hip, in the order a batch runs them.
+// The data of run_batch (hunt.hip, the only includer): what is fixed for a batch and how its workspaces are carved up (what one
+// attempt decides and what survives a repeat: Attempt, hunt_hints.hpp).  The functions that use them are in hunt.hip, in the order a batch runs them.
 #pragma once
 #include <type_traits>
 
@@ -162,35 +162,11 @@ struct FetchLayout {
   }
 };
 
-// The state that survives a repeat of the batch, what one attempt decided, and the forms reported in the result.
-struct Attempt {
-  // survives a repeat (start_caps; raised by review_attempt)
-  u32 shard_cap = 0;
-  u64 hit_cap = 0;
-  u32 flat_req = 0;  // slices of the flat Sel region asked for
-  u64 walk_cap = 0;  // room of the walker's group list (k_walk_list)
-  bool force_generic = false, force_jobs = false, force_short2 = false;
-  // decided per attempt: by decide_attempt at its top, unless a stage is named
-  bool fused = false;          // the flat search kernel settles the select stage as well
-  u32 flat_cap = 0;
-  bool generic_on = false;     // the generic search / select kernels run
-  bool walker_on = true;       // ... k_search among them (edit distance 2 leaves it out when the handle's batches have no group for it)
-  bool long2 = false;          // k_search2p's LONG2 body
-  bool prep_in = false;        // k_search1s settles the `take` values too (TAKE form)
-  bool with_ctx_hits = false;  // hits of the job kernels leave with their context characters
-  bool keys_on = false;        // launch_search, after the WS_SELKEY reserve: this attempt's k_search1s wrote the kept strings' keys (FlatSel::key)
-  bool jobs_on = false;        // launch_locate: the job kernels run (stays false in count mode, which has no locate stage)
-  u32 direct_ctx = 0;          // launch_locate (needs keys_on): k_locate hands a single occurrence's context on itself
-  // reported in the result, of the last attempt
-  u32 flat_form = 0;    // which flat search kernel was launched: dg_hunt_result::flat_kernel_form
-  u32 verify_form = 0;  // ... and which k_verify_memo instantiation: dg_hunt_result::verify_kernel_form
-  u64 nleaf = 0, nhits = 0;
-};
-
 // The batch's device pointers: the fixed ones (init_batch), and the ones an attempt's capacities move (reserve_attempt)
 struct BatchBufs {
   Batch b;
   u64 nxs = 0;
+  BatchFacts facts;  // what the rules of hunt_hints.hpp read of the batch (init_batch)
   u64 *grp_off, *hit_off, *scan_buf;
   Counters* ctr;
   u32 *grp_cnt, *nsel, *selbase;

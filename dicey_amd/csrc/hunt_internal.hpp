@@ -66,8 +66,7 @@ DG_DEV u8 ascii_of(u32 code) { return code == 0 ? 'A' : code == 1 ? 'C' : code =
 
 
 // Counters and the leaf allocator are sharded by workgroup: a single hot word serialises at ~11 ns per atomic, which
-// is milliseconds once hundreds of thousands of wavefronts report.
-static constexpr u32 NSHARD = 1024;
+// is milliseconds once hundreds of thousands of wavefronts report.  (NSHARD: hunt_hints.hpp, beside the capacities per shard)
 struct Counters {
   u32 overflow;          // set by k_leaf_overflow when a shard's region was too small: later kernels do nothing
   u32 pad_[15];
@@ -108,8 +107,6 @@ enum CounterWord : u32 {
   CW_N_WALK = 10,    // groups listed for the walker (k_walk_list)
   CW_N_KEEP = 11,    // strands listed for k_nkeep (k_walk_list)
 };
-// dg_index::ev: the events run_batch records on the lane's stream, in stream order except EV_FLAT_END (behind the flat search kernel)
-enum BatchEvent : int { EV_BEGIN = 0, EV_PREPARED, EV_SEARCHED, EV_GROUPS_SCANNED, EV_SELECTED, EV_HITS_SCANNED, EV_LOCATED, EV_END, EV_FLAT_END, EV_COUNT };
 
 struct HitSeed {  // 16 bytes, read as one uint4
   u32 pos;  // text position of the neighbourhood string
@@ -117,8 +114,6 @@ struct HitSeed {  // 16 bytes, read as one uint4
   u32 len;  // its length
   u32 sel;  // slot of the kept string (Sel) the hit stems from: hits of one slot share query, strand and string
 };
-
-enum WsSlot { WS_QB = 0, WS_QOFF, WS_FW, WS_RV, WS_QSEQ, WS_QMETA, WS_LEAF, WS_LEAFG, WS_SEL, WS_GRP, WS_MISC, WS_SEEDS, WS_HITS, WS_ALN, WS_CUM, WS_SCR, WS_JOBS, WS_DP, WS_PRIM, WS_GINFO, WS_XS, WS_OPS, WS_PACK, WS_CAP, WS_WALK, WS_SELKEY };
 
 // one located hit after the `dicey search` stage
 struct SiteRaw {

@@ -9,20 +9,7 @@ __global__ void k_leaf_overflow(Counters* ctr, u32 shard_cap, u32 surv_cap) {  /
   u32 k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < NSHARD && (ctr->leaf_cnt[k] > shard_cap || ctr->surv_cnt[k] > surv_cap)) atomicOr(&ctr->overflow, 1u);
 }
-// what the host needs at the end of a batch, in 64 bytes instead of the 36 KB of sharded counters
-struct Summary {
-  unsigned long long nleaf, worst_shard, steps, lookups, sa_reads, win_bytes, nhits, overflow, refused, too_long, probes, worst_surv;
-  unsigned long long jobs_big, jobs_small;  // repeat-rich strings queued by k_locate (workgroup / wavefront jobs)
-  unsigned long long worst_sel;             // fullest slice of the flat Sel region (k_search1s)
-  unsigned long long fused_leaves;          // occurring strings k_search1s kept in LDS (they never became Leaf records)
-  unsigned long long n_generic;             // groups searched outside the flat distance-1 kernel (k_prepare)
-  unsigned long long n_nwin;                // flag: N-bearing strands that walk in window mode (k_prepare)
-  unsigned long long n_short2;              // distance 2: queries k_search2p<., true> left to the walker for their length (k_prepare)
-  unsigned long long n_walk;                // groups listed for the walker (k_walk_list)
-#ifdef DG_TOPK_PROFILE
-  unsigned long long prof[24];
-#endif
-};
+// The batch summary (struct Summary, hunt_hints.hpp: what the host needs at the end of a batch, instead of the 36 KB of sharded counters).
 // Totals straight into the pinned host record (no atomics over the bus, no separate copy); the host reads it
 // after the batch's single stream synchronisation.  The batch's last kernel: it also leaves the counters ZEROED for the next
 // batch (which then needs no memset in front).  One workgroup.

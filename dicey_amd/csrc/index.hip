@@ -995,13 +995,7 @@ int dg_index_share(dg_index* src, dg_index** out) {
   std::memcpy(ix->code_len, src->code_len, sizeof ix->code_len);
   ix->file_bytes = src->file_bytes;
   ix->hbm_bytes = 0;
-  ix->shard_cap_hint = src->shard_cap_hint;
-  ix->hit_cap_hint = src->hit_cap_hint;
-  ix->flat_cap_hint = src->flat_cap_hint;
-  ix->generic_hint = src->generic_hint;
-  ix->jobs_hint = src->jobs_hint;
-  ix->fetch_hits_hint = src->fetch_hits_hint;
-  ix->fused_leaves_hint = src->fused_leaves_hint;
+  ix->hints = src->hints.inherited();
   // DICEY_EXP_PRIO (measurement aid, r06): the shares of an index — its internal lanes — get stream priorities in turn (highest,
   // lowest, highest, ...) while the index's own stream stays at the default, so that the lanes' search kernels do not share the chip
   // evenly (which keeps the lanes in step: DESIGN "lanes")

@@ -6,6 +6,14 @@
 #include "common.hpp"
 #include "devfm.hpp"
 #include "experiments.hpp"
+#include "hunt_hints.hpp"
+
+namespace dg {
+// dg_index::ws: the grow-only batch workspaces (hunt.hip / seam.hip / search.hip)
+enum WsSlot { WS_QB = 0, WS_QOFF, WS_FW, WS_RV, WS_QSEQ, WS_QMETA, WS_LEAF, WS_LEAFG, WS_SEL, WS_GRP, WS_MISC, WS_SEEDS, WS_HITS, WS_ALN, WS_CUM, WS_SCR, WS_JOBS, WS_DP, WS_PRIM, WS_GINFO, WS_XS, WS_OPS, WS_PACK, WS_CAP, WS_WALK, WS_SELKEY, WS_COUNT };
+// dg_index::ev: the events run_batch records on the lane's stream, in stream order except EV_FLAT_END (behind the flat search kernel)
+enum BatchEvent : int { EV_BEGIN = 0, EV_PREPARED, EV_SEARCHED, EV_GROUPS_SCANNED, EV_SELECTED, EV_HITS_SCANNED, EV_LOCATED, EV_END, EV_FLAT_END, EV_COUNT };
+}  // namespace dg
 
 // Test / development switches of the hunt pipeline (environment variables).  Read ONCE per batch, on the thread that calls the
 // library (the submitting thread for dg_hunt_submit batches) — never on the lanes' helper threads, where getenv would race with a
@@ -32,21 +40,9 @@ struct dg_index {
   uint64_t file_bytes = 0, hbm_bytes = 0;
   double load_seconds = 0, derive_seconds = 0;
   // grow-only batch workspaces (see hunt.hip / seam.hip for the slot meaning)
-  static constexpr int NWS = 26;
-  dg::DevBuf ws[NWS];
-  hipEvent_t ev[9] = {nullptr};  // [8]: end of the flat distance-1 kernel
-  uint32_t flat_cap_hint = 0;   // slice capacity of the flat Sel region that was enough so far (hunt.hip)
-  uint32_t shard_cap_hint = 0;  // capacities that were enough for the previous batch (hunt.hip)
-  uint64_t hit_cap_hint = 0;
-  bool generic_hint = true;      // the previous distance-1 batch had work for the kernels outside k_search1s (hunt.hip run_batch)
-  bool jobs_hint = true;         // the previous batch queued strings for the locate job kernels
-  uint32_t walk_hint = 0;        // groups the previous batch listed for the walker (k_walk_list)
-  uint32_t nwin_sticky = 0;      // batches the walker keeps its root split beside the flat distance-1 kernel (N-bearing strands in window mode)
-  uint32_t short2_sticky = 0;    // distance 2: batches left on k_search2p's r04 body after one that held queries too short for LONG2
-  uint32_t generic_sticky = 1, jobs_sticky = 1;  // batches the two hints stay on after the last batch that needed them
-  uint64_t jobs_big_hint = 0;    // repeat-rich strings (workgroup locate jobs) of the previous batch
-  uint64_t fused_leaves_hint = 0;  // occurring strings the previous distance-1 batch held in k_search1s' LDS lists (+ generic leaves)
-  uint64_t fetch_hits_hint = 0;  // hits of the previous fetched batch (+3 %): this many are copied to the host before the batch's synchronisation
+  dg::DevBuf ws[dg::WS_COUNT];
+  hipEvent_t ev[dg::EV_COUNT] = {nullptr};
+  dg::Hints hints;  // what the handle learnt from its earlier hunt batches (hunt_hints.hpp; hunt.hip run_batch)
   // dg_hunt_device: the (offsets pointer, count, bytes) of the previous call and the longest query it held; a repeated
   // call skips reading the offsets back, and k_prepare reports any query longer than this bound (hunt.hip)
   // (r04: a small table, not one entry — a caller that cycles through a ring of resident batches finds each of them again)
@@ -77,9 +73,8 @@ struct dg_index {
   // lane that runs its first batch does not repeat it for a capacity another lane has already learnt.
   struct SharedHints {
     std::mutex mu;
-    uint32_t flat_cap = 0, shard_cap = 0, generic_sticky = 0, jobs_sticky = 0;
-    uint64_t hit_cap = 0, jobs_big = 0, fused_leaves = 0, fetch_hits = 0;
-    bool valid = false;
+    dg::Hints h;         // Hints::publish writes it, Hints::merge reads it ...
+    bool valid = false;  // ... once a lane has published
     // the lanes' common timeline (dg_hunt_result::t_search_*): two base events used in turn, a new one every few seconds
     hipEvent_t ev_base[2] = {nullptr, nullptr};
     uint32_t base_gen = 0;
@@ -91,6 +86,13 @@ struct dg_index {
   struct Worker;                      // the helper thread that drives dg_hunt_submit batches (hunt.hip)
   Worker* worker = nullptr;
   void stop_worker();
+  bool any_lane_busy() {              // a dg_hunt_submit batch is in flight on the handle or one of its lanes
+    if (busy.load()) return true;
+    std::lock_guard<std::mutex> lk(lanes_mu);
+    for (dg_index* l : lanes)
+      if (l && l->busy.load()) return true;
+    return false;
+  }
   const void* ctr_clean = nullptr;
   unsigned long long ctr_clean_gen = 0;
   std::vector<uint64_t> cum_cache;    // cumulative sequence starts currently resident in WS_CUM

@@ -173,14 +173,6 @@ __global__ void k_run_values(const u32* out, u64 a, const u32* starts, const uns
   val[t] = out[a + starts[t]];
 }
 
-static bool any_lane_busy(dg_index* ix) {  // as hunt.hip's
-  if (ix->busy.load()) return true;
-  std::lock_guard<std::mutex> lk(ix->lanes_mu);
-  for (dg_index* l : ix->lanes)
-    if (l && l->busy.load()) return true;
-  return false;
-}
-
 // default ranks per k_heads_mm launch and default W (rows verified on the text): DESIGN.md §10 has the measurements behind both
 static constexpr u64 MM_HEAD_CHUNK = 1ULL << 24;
 static constexpr u32 MM_NARROW = 8;
@@ -454,7 +446,7 @@ static int query_args_check(const char* who, dg_index* ix, const uint8_t* seqs, 
   for (size_t i = 0; i < nseq; ++i)
     if (off[i] > off[i + 1]) return fail(DG_EINVAL, "%s: offsets decrease at record %llu", who, (unsigned long long)i);
   if (ix->view.n < 2 || ix->view.n > 0xFFFFFFFFull) return fail(DG_ELIMIT, "%s: index of %llu suffixes", who, (unsigned long long)ix->view.n);
-  if (any_lane_busy(ix)) return fail(DG_EINVAL, "%s: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)", who);
+  if (ix->any_lane_busy()) return fail(DG_EINVAL, "%s: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)", who);
   return DG_OK;
 }
 
@@ -662,7 +654,7 @@ static int map_open(dg_index* ix, const dg_map_params* p, u32 mismatches, int mo
   const char* who = mode ? "dg_min_unique" : "dg_mappability";
   if (p->k < 10 || p->k > 1000) return fail(DG_ELIMIT, "%s: %s = %u outside 10..1000", who, mode ? "max_k" : "k", p->k);
   if (ix->view.n < 2 || ix->view.n > 0xFFFFFFFFull) return fail(DG_ELIMIT, "%s: index of %llu suffixes", who, (unsigned long long)ix->view.n);
-  if (any_lane_busy(ix)) return fail(DG_EINVAL, "%s: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)", who);
+  if (ix->any_lane_busy()) return fail(DG_EINVAL, "%s: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)", who);
   DG_HIP(hipSetDevice(ix->device));
   dg_map* m = new dg_map;
   m->device = ix->device;

@@ -12,14 +12,14 @@ planted one at a time against a running census of every candidate of every satur
 past its target is planted with another spacer or left out.  tests/test_select_shapes_host.py repeats the census from scratch on
 the finished text.
 
-The batch layout restated (dicey_amd/csrc/hunt.hip, launch_flat1 and start_caps):
+The batch layout restated (dicey_amd/csrc/hunt.hip launch_flat1, hunt_hints.hpp start_caps):
 
     const u32 ipg = std::min(pl.maxlen, 31u), ...                                                               // hunt.hip:843
     const u32 gpw = at.prep_in ? (std::min(16u, 256u / ipg) & ~1u) : std::min(16u, 256u / ipg);                 // hunt.hip:845
     const dim3 g1(ceil_div(pl.ngrp, gpw)), b1(256);                                                             // hunt.hip:854
-    const u32 lcap = ... (ix->fused_leaves_hint > 48ull * g1.x ? FUSED_LCAP : FUSED_LCAP / 2);                  // hunt.hip:859
-    at.shard_cap = std::max<u32>(ix->shard_cap_hint, (u32)std::max<u64>(64, (16 * nq + nxs / 8) / NSHARD));     // hunt.hip:738
-    at.flat_req = ix->flat_cap_hint ? ix->flat_cap_hint : at.shard_cap;                                         // hunt.hip:742
+    const u32 lcap = ... (ix->hints.fused_leaves > 48ull * g1.x ? FUSED_LCAP : FUSED_LCAP / 2);                 // launch_flat1
+    at.shard_cap = std::max<u32>(h.shard_cap, (u32)std::max<u64>(64, (16 * f.nq + f.nxs / 8) / NSHARD));       // start_caps
+    at.flat_req = h.flat_cap ? h.flat_cap : at.shard_cap;                                                       // start_caps
     const u32 g_first = blockIdx.x * gpw;  ...  const u32 shard = blockIdx.x & (NSHARD - 1);                    // hunt_search.hpp:685, 745
 
 group 2 i + strand belongs to query i; workgroup = group // gpw; Sel slice = workgroup & 1023; a slice of a fresh handle holds 64 kept

@@ -80,9 +80,9 @@ def pads_of(batch):
 
 
 def settle(h, name, batch, ham):
-    """A handle's first batch runs with the generic kernels (dg_index::generic_hint starts true, generic_sticky 1: index_internal.hpp:41,
-    46); a batch that has no work for them turns them off for the next one.  The batch's own padding is that batch: form 2 at distance
-    1 (k_take a launch of its own), the LONG2 body at distance 2."""
+    """A handle's first batch runs with the generic kernels (Hints::generic starts at 1: hunt_hints.hpp); a batch that has no work for
+    them turns them off for the next one.  The batch's own padding is that batch: form 2 at distance 1 (k_take a launch of its own),
+    the LONG2 body at distance 2."""
     hunt(h, name, pads_of(batch), ham, 2 if S.genome(name)["d"] == 1 else 7, 0, limits=[1000])
 
 
@@ -132,7 +132,7 @@ def test_c_the_list_of_256_holds_256_and_hands_257_over(fm9, ham):
 
 @pytest.mark.parametrize("ham", MODES)
 def test_d_the_list_of_512_holds_512_and_hands_513_over_in_rounds(fm9, ham):
-    """right behind a batch whose census was 513 the list has 512 entries (fused_leaves_hint): 512 fit; 513 overflow, and with more than
+    """right behind a batch whose census was 513 the list has 512 entries (Hints::fused_leaves): 512 fit; 513 overflow, and with more than
     512 survivors the workgroup sends its leaves out through the multi-round queue"""
     name = occ(ham)
     b = S.genome(name)["batches"]
