@@ -1,8 +1,11 @@
 // dg_index_open / dg_index_close / dg_index_stats: load the sdsl csa_wt<> file unchanged into HBM and derive the
 // search layouts on the device.  Replaces load_from_checked_file (reference src/hunter.h:253-260, src/silica.h:340-347).
 #include <chrono>
+#include <memory>
 
+#include "dev_mem.hpp"
 #include "devfm.hpp"
+#include "index_plan.hpp"
 #include "index_internal.hpp"
 #include <rocprim/device/device_scan.hpp>
 
@@ -376,11 +379,7 @@ static int build_filter(dg_index* ix, KFilter& kf, u32 k, const uint2* tab, u32*
     const u32 s = kf.s[r];
     u32* bm = nullptr;
     if (r == 0 && copy0) bm = copy0;
-    else {
-      DG_HIP(big_alloc((void**)&bm, nwords * 4 + 64, ix->stream));
-      ix->owned.push_back(bm);
-      ix->hbm_bytes += nwords * 4 + 64;
-    }
+    else DG_TRY(ix->own((void**)&bm, plan::filter_copy_bytes(k)));
     if (r == 0 && copy0) {
       // filled by the caller
     } else if (r == 0) {
@@ -554,21 +553,26 @@ struct PhaseClock {  // DICEY_TIMING=1: host wall clock of the load phases on st
   }
 };
 
-static int derive_layouts(dg_index* ix, const SdslCsa& c, u32 flags) {
+// ------------------------------------------------------------------------------------------------------------
+// The open as stages (derive_layouts below is their list).  A stage owns its temporaries through a scratch local to it; what stays is
+// the index's from dg_index::own / try_own on; the decisions between the launches are index_plan.hpp's.  A stage returns with the
+// stream synchronised, so the free bytes the next one asks for are the ones it left.
+// ------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(OccBlock) == 64 && plan::MAXPLV == FmView::MAXPLV && plan::PLV_LINE == FmView::PLV_LINE, "index_plan.hpp");
+static constexpr u32 TB = 256;
+
+// Occ blocks from the decoded BWT; C[] of the file must agree with what the decoded BWT holds
+static int stage_occ(dg_index* ix, const SdslCsa& c) {
   FmView& f = ix->view;
-  PhaseClock pc;
-  const u64 n = f.n;
-  const u64 nblk = (n >> 7) + 1, nhalf = nblk * 2;
+  const u64 nblk = plan::occ_blocks(f.n), nhalf = nblk * 2;
   const u64 nchunk = (nhalf + HALF_PER_CHUNK - 1) / HALF_PER_CHUNK;
   OccBlock* occ = nullptr;
-  u32 *half_cnt = nullptr, *chunk = nullptr, *sa = nullptr, *bad = nullptr;
-  u8* text = nullptr;
-  DG_HIP(big_alloc((void**)&occ, nblk * sizeof(OccBlock), ix->stream));
-  ix->owned.push_back(occ);
+  u32 *half_cnt = nullptr, *chunk = nullptr;
+  DG_TRY(ix->own((void**)&occ, nblk * sizeof(OccBlock)));
   DG_HIP(hipMemsetAsync(occ, 0, nblk * sizeof(OccBlock), ix->stream));
-  DG_HIP(big_alloc((void**)&half_cnt, nhalf * 4, ix->stream));
-  DG_HIP(hipMalloc((void**)&chunk, nchunk * 16));
-  const u32 TB = 256;
+  StreamScratch tmp(ix->stream);  // gone before the text is allocated
+  DG_TRY(tmp.big((void**)&half_cnt, nhalf * 4));
+  DG_TRY(tmp.small((void**)&chunk, nchunk * 16));
   hipLaunchKernelGGL(k_decode_bwt, dim3(ceil_div(nhalf, TB)), dim3(TB), 0, ix->stream, f, occ, half_cnt, nhalf);
   hipLaunchKernelGGL(k_chunk_totals, dim3(ceil_div(nchunk, TB)), dim3(TB), 0, ix->stream, half_cnt, nhalf, chunk, nchunk);
   std::vector<u32> tot(nchunk * 4);
@@ -581,7 +585,6 @@ static int derive_layouts(dg_index* ix, const SdslCsa& c, u32 flags) {
       tot[t * 4 + s] = (u32)run[s];
       run[s] += v;
     }
-  // C[] of the file must agree with what the decoded BWT holds
   static const u8 acgt[4] = {'A', 'C', 'G', 'T'};
   for (int s = 0; s < 4; ++s) {
     u32 cc = c.char2comp[acgt[s]];
@@ -596,35 +599,37 @@ static int derive_layouts(dg_index* ix, const SdslCsa& c, u32 flags) {
                      nblk);
   f.occ = occ;
   DG_HIP(hipStreamSynchronize(ix->stream));
-  big_free(half_cnt, ix->stream);
-  DG_HIP(hipFree(chunk));
-  pc.lap("occ blocks");
+  return DG_OK;
+}
 
-  DG_HIP(big_alloc((void**)&text, n + 64, ix->stream));
-  ix->owned.push_back(text);
-  DG_HIP(big_alloc((void**)&sa, n * 4 + 64, ix->stream));
-  ix->owned.push_back(sa);
+// Text and suffix array: in one walk with the inverse suffix array, which is then sorted (large indexes), or in two independent walks
+static int stage_text_sa(dg_index* ix) {
+  FmView& f = ix->view;
+  const u64 n = f.n;
+  u8* text = nullptr;
+  u32* sa = nullptr;
+  DG_TRY(ix->own((void**)&text, plan::text_bytes(n)));
+  DG_TRY(ix->own((void**)&sa, plan::sa_bytes(n)));
   bool sorted_sa = false;
   if (n > (1u << 16)) {
-    // text and inverse suffix array in one walk, suffix array by sorting (isa[p], p)
-    u32* isa = nullptr;
-    if (big_alloc((void**)&isa, n * 4 + 64, ix->stream) == hipSuccess) {
-      hipLaunchKernelGGL(k_derive_text_isa, dim3(ceil_div(f.n_isa_samp, TB)), dim3(TB), 0, ix->stream, f, text, isa);
-      const int rc = derive_sa_by_sort(ix->stream, isa, n, sa);
-      big_free(isa, ix->stream);
-      if (rc == DG_OK) {
-        u32* badp = nullptr;
-        u32 hbad = 0;
-        DG_HIP(hipMalloc((void**)&badp, 4));
-        DG_HIP(hipMemsetAsync(badp, 0, 4, ix->stream));
-        hipLaunchKernelGGL(k_check_sa_samples, dim3(ceil_div(f.n_sa_samp, TB)), dim3(TB), 0, ix->stream, f, (const u32*)sa, badp);
-        DG_HIP(hipMemcpyAsync(&hbad, badp, 4, hipMemcpyDeviceToHost, ix->stream));
-        DG_HIP(hipStreamSynchronize(ix->stream));
-        DG_HIP(hipFree(badp));
-        if (hbad) return fail(DG_EFORMAT, "index self-check: %u suffix-array samples of the file disagree with its inverse samples", hbad);
-        sorted_sa = true;
-      } else if (rc != DG_ENODEV && rc != DG_ENOMEM) return rc;
-    } else (void)hipGetLastError();
+    int rc = DG_ENOMEM;  // (no room for isa, like no room for the sort: the two walks)
+    {  // text and inverse suffix array in one walk, suffix array by sorting (isa[p], p); isa is gone before the table is sized
+      StreamScratch tmp(ix->stream);
+      u32* isa = nullptr;
+      if (tmp.big((void**)&isa, plan::sa_bytes(n)) == DG_OK) {
+        hipLaunchKernelGGL(k_derive_text_isa, dim3(ceil_div(f.n_isa_samp, TB)), dim3(TB), 0, ix->stream, f, text, isa);
+        rc = derive_sa_by_sort(ix->stream, isa, n, sa);
+      } else (void)hipGetLastError();
+    }
+    if (rc == DG_OK) {
+      DevWord bad(ix->stream);
+      u32 hbad = 0;
+      DG_TRY(bad.init(0));
+      hipLaunchKernelGGL(k_check_sa_samples, dim3(ceil_div(f.n_sa_samp, TB)), dim3(TB), 0, ix->stream, f, (const u32*)sa, bad.p);
+      DG_TRY(bad.read(&hbad));
+      if (hbad) return fail(DG_EFORMAT, "index self-check: %u suffix-array samples of the file disagree with its inverse samples", hbad);
+      sorted_sa = true;
+    } else if (rc != DG_ENODEV && rc != DG_ENOMEM) return rc;
   }
   if (!sorted_sa) {  // the two independent walks (small indexes, low memory, debugging builds)
     hipLaunchKernelGGL(k_derive_text, dim3(ceil_div(f.n_isa_samp, TB)), dim3(TB), 0, ix->stream, f, text);
@@ -634,202 +639,207 @@ static int derive_layouts(dg_index* ix, const SdslCsa& c, u32 flags) {
   f.sa = sa;
   DG_HIP(hipStreamSynchronize(ix->stream));
   DG_HIP(hipGetLastError());
-  pc.lap("text + suffix array");
-  {  // the shortest run of 'N' (one streaming pass over the text)
-    u32* d_min = nullptr;
-    u32 h_min = 64;
-    DG_HIP(hipMalloc((void**)&d_min, 4));
-    DG_HIP(hipMemcpyAsync(d_min, &h_min, 4, hipMemcpyHostToDevice, ix->stream));
-    hipLaunchKernelGGL(k_nrun_min, dim3((u32)std::min<u64>(ceil_div(n, TB), 1u << 16)), dim3(TB), 0, ix->stream, (const u8*)text, n, d_min);
-    DG_HIP(hipMemcpyAsync(&h_min, d_min, 4, hipMemcpyDeviceToHost, ix->stream));
-    DG_HIP(hipStreamSynchronize(ix->stream));
-    DG_HIP(hipFree(d_min));
-    f.nrun_min = exp_env("DICEY_NO_NRUN_PRUNE") ? 0u : h_min;
-    pc.lap("shortest N run");
+  return DG_OK;
+}
+
+// the shortest run of 'N' (one streaming pass over the text)
+static int stage_nrun(dg_index* ix) {
+  FmView& f = ix->view;
+  DevWord dmin(ix->stream);
+  u32 h_min = 64;
+  DG_TRY(dmin.init(h_min));
+  hipLaunchKernelGGL(k_nrun_min, dim3((u32)std::min<u64>(ceil_div(f.n, TB), 1u << 16)), dim3(TB), 0, ix->stream, f.text, f.n, dmin.p);
+  DG_TRY(dmin.read(&h_min));
+  f.nrun_min = exp_env("DICEY_NO_NRUN_PRUNE") ? 0u : h_min;
+  return DG_OK;
+}
+
+struct TableBuild {
+  uint2* tab = nullptr;  // (lo, hi) pairs until stage_table_pack
+  u32* f2 = nullptr;     // copy 0 of the long filter: its bits are set by the pass that fills the table
+  plan::TableOrders o{0, 0};
+};
+// The K-mer table in its orders (plan::table_orders) and, with it, copy 0 of the long filter
+static int stage_table(dg_index* ix, u32 flags, PhaseClock& pc, TableBuild& t) {
+  FmView& f = ix->view;
+  plan::TableFacts tf;
+  tf.n = f.n;
+  tf.flags = flags;
+  size_t free_b = 0, total_b = 0;
+  tf.have_mem = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+  tf.free_b = free_b;
+  if (const char* ek = std::getenv("DICEY_KMER_K")) tf.env_k = std::atoi(ek);  // tuning knobs: force the table order (8..17) ...
+  if (const char* ek = std::getenv("DICEY_KMER_K2")) {                         // ... / the long filter's (0 = none)
+    tf.env_k2_set = true;
+    tf.env_k2 = std::atoi(ek);
   }
-  if (!(flags & DG_OPEN_NO_KMER_TABLE)) {
-    // K = ceil(log4 n) clamped to [8,16]: about one expected occurrence per K-mer; 16 -> 34 GB, which is what the
-    // 288 GB of HBM are for
-    u32 K = 8;
-    while (K < 16 && (1ULL << (2 * K)) < n) ++K;
-    // What the rest of the HBM is spent on (DESIGN.md "long filter"): one character more for the table when the device has
-    // room (K = 17, 137 GB, on a 3.1 Gb genome: one interval extension fewer per surviving string), and a presence filter of
-    // order K2 = ceil(log4 n) + 2 in four permuted copies (4 x 8.6 GB at K2 = 18) in front of everything — a random 18-mer of
-    // a 3.1 Gb genome occurs with p = 0.04, a 16-mer with 0.51, a 17-mer with 0.17.  r02 measured K / K2 = 16/19, 16/18 and
-    // 17/18 on the bench workloads; 17/18 is the fastest at both distances.
-    u32 K2 = 0;
-    {
+  tf.no_filter = exp_env("DICEY_NO_KMER_FILTER");
+  t.o = plan::table_orders(tf);
+  pc.lap("table order (hipMemGetInfo)");
+  DG_TRY(ix->own((void**)&t.tab, plan::table_bytes(t.o.K)));
+  pc.lap("table hipMalloc");
+  DG_HIP(hipMemsetAsync(t.tab, 0, plan::table_bytes(t.o.K), ix->stream));
+  if (t.o.K2) {
+    DG_TRY(ix->own((void**)&t.f2, plan::filter_copy_bytes(t.o.K2)));
+    DG_HIP(hipMemsetAsync(t.f2, 0, plan::filter_copy_bytes(t.o.K2), ix->stream));
+  }
+  hipLaunchKernelGGL(k_kmer_table_wave, dim3(ceil_div(f.n, TB)), dim3(TB), 0, ix->stream, f, t.tab, t.o.K, t.o.K2, t.f2);
+  DG_HIP(hipStreamSynchronize(ix->stream));
+  DG_HIP(hipGetLastError());
+  f.ktab = t.tab;
+  f.K = t.o.K;
+  return DG_OK;
+}
+
+// The characters in front of every suffix (2 n bytes): built with the table, i.e. for handles that search batches.  With the same
+// gather: the suffix array with context (8 n bytes, FmView::sax) for the locate job kernels — handles that have the block minima (i.e.
+// the top-k locate) and the room; DICEY_NO_SAX leaves it out (the tests run both ways: hits of repeat-rich strings then read their
+// context from the text as before r06)
+static int stage_pre5_sax(dg_index* ix, u32 flags) {
+  FmView& f = ix->view;
+  const u64 n = f.n;
+  u16* pre = nullptr;
+  uint2* sax = nullptr;
+  if (!ix->try_own((void**)&pre, plan::pre5_bytes(n))) return DG_OK;
+  if (!(flags & DG_OPEN_COMPACT) && !exp_env("DICEY_NO_SAX") && !exp_env("DICEY_NO_SA_MINIMA")) {
+    size_t free_b = 0, total_b = 0;
+    const bool have = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
+    if (!(plan::sax_fits(n, have, free_b) && ix->try_own((void**)&sax, plan::sax_bytes(n)))) (void)hipGetLastError();
+  }
+  hipLaunchKernelGGL(k_pre5, dim3(ceil_div(n, TB)), dim3(TB), 0, ix->stream, f.sa, f.text, n, pre, sax);
+  DG_HIP(hipStreamSynchronize(ix->stream));
+  DG_HIP(hipGetLastError());
+  f.pre5 = pre;
+  f.sax = sax;
+  return DG_OK;
+}
+
+// Prefix levels over the records (FmView::plv): X = 2^16, 2^18, ... below n — 64 n / 448 bytes of directory and 8 X bytes of records per
+// level (GRCh38: 8 levels, 3.5 + 11.5 GB); DICEY_NO_PLV leaves them out (tests: every repeat-rich string then walks the block minima).
+// A level's two blocks are the index's only once the level is complete: the first level that does not fit, or whose scan fails, ends
+// the list and leaves nothing behind (its scratch synchronises the stream before it releases them).
+static int stage_prefix_levels(dg_index* ix) {
+  FmView& f = ix->view;
+  const u64 n = f.n, nlines = plan::plv_lines(n);
+  StreamScratch tmp(ix->stream);
+  u32 *cnt = nullptr, *before = nullptr;
+  void* scan = nullptr;
+  size_t scan_bytes = 0;
+  (void)rocprim::exclusive_scan(nullptr, scan_bytes, (const u32*)nullptr, (u32*)nullptr, 0u, nlines, rocprim::plus<u32>(), ix->stream);
+  if (tmp.small((void**)&cnt, nlines * 4) == DG_OK && tmp.small((void**)&before, nlines * 4) == DG_OK &&
+      tmp.small(&scan, scan_bytes ? scan_bytes : 16) == DG_OK) {
+    for (const u64 x : plan::plv_sizes(n)) {
       size_t free_b = 0, total_b = 0;
       const bool have = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-      const u64 slack = (u64)std::min<u64>(48ULL << 30, n * 16 + (64u << 20));
-      const u64 f2_b = 4 * ((1ULL << (2 * (K + 2))) >> 3);
-      u64 need = (8ULL << (2 * K)) + slack;
-      if (have && free_b > need + f2_b) {
-        K2 = K + 2;
-        need += f2_b;
-      }
-      if ((flags & DG_OPEN_BIG_TABLE) && have && (1ULL << (2 * K)) < n * 2 && free_b > need - (8ULL << (2 * K)) + (8ULL << (2 * (K + 1)))) ++K;
+      if (!plan::plv_level_fits(n, x, have, free_b)) break;
+      StreamScratch level(ix->stream);
+      u64* dir = nullptr;
+      uint2* rec = nullptr;
+      if (level.big((void**)&dir, plan::plv_dir_bytes(n)) != DG_OK || level.big((void**)&rec, plan::plv_rec_bytes(x)) != DG_OK) break;
+      hipLaunchKernelGGL(k_plv_bits, dim3(ceil_div(nlines, 4)), dim3(256), 0, ix->stream, f.sa, n, x, dir, cnt, nlines);
+      if (rocprim::exclusive_scan(scan, scan_bytes, (const u32*)cnt, before, 0u, nlines, rocprim::plus<u32>(), ix->stream) != hipSuccess) break;
+      hipLaunchKernelGGL(k_plv_fill, dim3(ceil_div(nlines, 4)), dim3(256), 0, ix->stream, f.sax, (const u32*)before, dir, rec, nlines);
+      DG_HIP(hipStreamSynchronize(ix->stream));
+      DG_HIP(hipGetLastError());
+      level.keep();
+      ix->adopt(dir, plan::plv_dir_bytes(n));
+      ix->adopt(rec, plan::plv_rec_bytes(x));
+      f.plv[f.nplv++] = {dir, rec, x};
     }
-    if (const char* ek = std::getenv("DICEY_KMER_K")) {  // tuning knobs: force the table order (8..17) / the long filter's (0 = none)
-      int v = std::atoi(ek);
-      if (v >= 8 && v <= 17) {
-        K = (u32)v;
-        if (K2 && K2 <= K) K2 = K + 1;
-      }
-    }
-    if (const char* ek = std::getenv("DICEY_KMER_K2")) {
-      int v = std::atoi(ek);
-      K2 = (v > (int)K && v <= 20) ? (u32)v : 0u;
-    }
-    if (exp_env("DICEY_NO_KMER_FILTER") || 2 * K2 < 17) K2 = 0;
-    pc.lap("table order (hipMemGetInfo)");
-    uint2* tab = nullptr;
-    u64 entries = 1ULL << (2 * K);
-    DG_HIP(big_alloc((void**)&tab, entries * sizeof(uint2), ix->stream));
-    ix->owned.push_back(tab);
-    pc.lap("table hipMalloc");
-    DG_HIP(hipMemsetAsync(tab, 0, entries * sizeof(uint2), ix->stream));
-    u32* f2 = nullptr;  // copy 0 of the long filter: its bits are set by the pass that fills the table
-    if (K2) {
-      const u64 f2_bytes = ((1ULL << (2 * K2)) >> 3) + 64;
-      DG_HIP(big_alloc((void**)&f2, f2_bytes, ix->stream));
-      ix->owned.push_back(f2);
-      ix->hbm_bytes += f2_bytes;
-      DG_HIP(hipMemsetAsync(f2, 0, f2_bytes, ix->stream));
-    }
-    hipLaunchKernelGGL(k_kmer_table_wave, dim3(ceil_div(n, TB)), dim3(TB), 0, ix->stream, f, tab, K, K2, f2);
-    DG_HIP(hipStreamSynchronize(ix->stream));
-    DG_HIP(hipGetLastError());
-    f.ktab = tab;
-    f.K = K;
-    ix->hbm_bytes += entries * sizeof(uint2);
+  }
+  (void)hipGetLastError();
+  return DG_OK;
+}
+
+// every reader of (lo, hi) pairs is done (the filters were derived from them): the entries take their final form
+static int stage_table_pack(dg_index* ix, const TableBuild& t) {
+  const u64 entries = 1ULL << (2 * t.o.K);
+  hipLaunchKernelGGL(k_ktab_pack, dim3((u32)std::min<u64>(ceil_div(entries, TB), 1u << 20)), dim3(TB), 0, ix->stream, t.tab, entries, ix->view.pre5);
+  DG_HIP(hipStreamSynchronize(ix->stream));
+  DG_HIP(hipGetLastError());
+  return DG_OK;
+}
+
+// block minima over the suffix array for the top-k locate (0.57 n bytes; one streaming pass over SA)
+static int stage_block_minima(dg_index* ix) {
+  FmView& f = ix->view;
+  u64 cnt = f.n;
+  const u32* prev = f.sa;
+  while (cnt > 8 && f.nlev < FmView::MAXLEV) {
+    const u64 nout = (cnt + 7) / 8, npad = ((nout + 7) & ~7ULL) + 8;
+    u32* lv = nullptr;
+    DG_TRY(ix->own((void**)&lv, npad * 4));
+    hipLaunchKernelGGL(k_block_min8, dim3(ceil_div(npad, TB)), dim3(TB), 0, ix->stream, prev, cnt, lv, nout, npad);
+    f.samin[f.nlev++] = lv;
+    prev = lv;
+    cnt = nout;
+  }
+  DG_HIP(hipStreamSynchronize(ix->stream));
+  DG_HIP(hipGetLastError());
+  return DG_OK;
+}
+
+static int stage_selfcheck(dg_index* ix) {
+  FmView& f = ix->view;
+  DevWord bad(ix->stream);
+  u32 hbad = 0;
+  DG_TRY(bad.init(0));
+  const u64 ns = f.n < (1u << 20) ? f.n : (1u << 20);
+  hipLaunchKernelGGL(k_selfcheck, dim3(ceil_div(ns, TB)), dim3(TB), 0, ix->stream, f, ns, bad.p);
+  DG_TRY(bad.read(&hbad));
+  if (hbad) return fail(DG_EFORMAT, "index self-check failed on %u of %llu sampled suffixes", hbad, (unsigned long long)ns);
+  return DG_OK;
+}
+
+static int derive_layouts(dg_index* ix, const SdslCsa& c, u32 flags) {
+  FmView& f = ix->view;
+  PhaseClock pc;
+  DG_TRY(stage_occ(ix, c));
+  pc.lap("occ blocks");
+  DG_TRY(stage_text_sa(ix));
+  pc.lap("text + suffix array");
+  DG_TRY(stage_nrun(ix));
+  pc.lap("shortest N run");
+  if (!(flags & DG_OPEN_NO_KMER_TABLE)) {
+    TableBuild t;
+    DG_TRY(stage_table(ix, flags, pc, t));
     pc.lap("table fill");
-    DG_TRY(build_filter(ix, f.kf, K, tab, nullptr));
+    DG_TRY(build_filter(ix, f.kf, t.o.K, t.tab, nullptr));
     pc.lap("presence filter");
-    if (K2) {
-      DG_TRY(build_filter(ix, f.kf2, K2, nullptr, f2));
+    if (t.o.K2) {
+      DG_TRY(build_filter(ix, f.kf2, t.o.K2, nullptr, t.f2));
       pc.lap("long presence filter");
     }
-    // the characters in front of every suffix (2 n bytes): built with the table, i.e. for handles that search batches
     if (!(flags & DG_OPEN_NO_PRE5) && !exp_env("DICEY_NO_PRE5")) {
-      u16* pre = nullptr;
-      if (big_alloc((void**)&pre, n * 2 + 64, ix->stream) == hipSuccess) {
-        ix->owned.push_back(pre);
-        ix->hbm_bytes += n * 2 + 64;
-        // with the same gather: the suffix array with context (8 n bytes, FmView::sax) for the locate job kernels — handles that
-        // have the block minima (i.e. the top-k locate) and the room; DICEY_NO_SAX leaves it out (the tests run both ways: hits of
-        // repeat-rich strings then read their context from the text as before r06)
-        uint2* sax = nullptr;
-        if (!(flags & DG_OPEN_COMPACT) && !exp_env("DICEY_NO_SAX") && !exp_env("DICEY_NO_SA_MINIMA")) {
-          size_t free_b = 0, total_b = 0;
-          if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > n * 8 + n * 2 + (4ULL << 30) &&
-              big_alloc((void**)&sax, n * 8 + 64, ix->stream) == hipSuccess) {
-            ix->owned.push_back(sax);
-            ix->hbm_bytes += n * 8 + 64;
-          } else {
-            sax = nullptr;
-            (void)hipGetLastError();
-          }
-        }
-        hipLaunchKernelGGL(k_pre5, dim3(ceil_div(n, TB)), dim3(TB), 0, ix->stream, (const u32*)sa, (const u8*)text, n, pre, sax);
-        DG_HIP(hipStreamSynchronize(ix->stream));
-        DG_HIP(hipGetLastError());
-        f.pre5 = pre;
-        f.sax = sax;
-        pc.lap(sax ? "preceding characters + suffix array with context" : "preceding characters");
-        // prefix levels over the records (FmView::plv): X = 2^16, 2^18, ... below n — 64 n / 448 bytes of directory and 8 X bytes
-        // of records per level (GRCh38: 8 levels, 3.5 + 11.5 GB); DICEY_NO_PLV leaves them out (tests: every repeat-rich string
-        // then walks the block minima)
-        if (sax && !exp_env("DICEY_NO_PLV")) {
-          const u64 nlines = n / FmView::PLV_LINE + 1;
-          u32 *cnt = nullptr, *before = nullptr;
-          void* tmp = nullptr;
-          size_t tmp_bytes = 0;
-          (void)rocprim::exclusive_scan(nullptr, tmp_bytes, (const u32*)nullptr, (u32*)nullptr, 0u, nlines, rocprim::plus<u32>(), ix->stream);
-          if (hipMalloc((void**)&cnt, nlines * 4) == hipSuccess && hipMalloc((void**)&before, nlines * 4) == hipSuccess &&
-              hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16) == hipSuccess) {
-            for (u32 lv = 0; lv < FmView::MAXPLV; ++lv) {
-              const u64 x = 1ULL << (16 + 2 * lv);
-              if (x >= n) break;
-              size_t free_b = 0, total_b = 0;
-              if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < nlines * 64 + x * 8 + (4ULL << 30)) break;
-              u64* dir = nullptr;
-              uint2* rec = nullptr;
-              if (big_alloc((void**)&dir, nlines * 64, ix->stream) != hipSuccess) break;
-              ix->owned.push_back(dir);
-              if (big_alloc((void**)&rec, x * 8 + 64, ix->stream) != hipSuccess) break;
-              ix->owned.push_back(rec);
-              ix->hbm_bytes += nlines * 64 + x * 8 + 64;
-              hipLaunchKernelGGL(k_plv_bits, dim3(ceil_div(nlines, 4)), dim3(256), 0, ix->stream, (const u32*)sa, n, x, dir, cnt, nlines);
-              if (rocprim::exclusive_scan(tmp, tmp_bytes, (const u32*)cnt, before, 0u, nlines, rocprim::plus<u32>(), ix->stream) != hipSuccess) break;
-              hipLaunchKernelGGL(k_plv_fill, dim3(ceil_div(nlines, 4)), dim3(256), 0, ix->stream, (const uint2*)sax, (const u32*)before, dir, rec, nlines);
-              DG_HIP(hipStreamSynchronize(ix->stream));
-              DG_HIP(hipGetLastError());
-              f.plv[lv].dir = dir;
-              f.plv[lv].rec = rec;
-              f.plv[lv].x = x;
-              f.nplv = lv + 1;
-            }
-          }
-          (void)hipGetLastError();
-          if (cnt) (void)hipFree(cnt);
-          if (before) (void)hipFree(before);
-          if (tmp) (void)hipFree(tmp);
-          pc.lap("prefix levels of the suffix array");
-        }
-      } else (void)hipGetLastError();
+      DG_TRY(stage_pre5_sax(ix, flags));
+      if (f.pre5) pc.lap(f.sax ? "preceding characters + suffix array with context" : "preceding characters");
+      if (f.sax && !exp_env("DICEY_NO_PLV")) {
+        DG_TRY(stage_prefix_levels(ix));
+        pc.lap("prefix levels of the suffix array");
+      }
     }
-    // every reader of (lo, hi) pairs is done (the filters above were derived from them): the entries take their final form
-    hipLaunchKernelGGL(k_ktab_pack, dim3((u32)std::min<u64>(ceil_div(entries, TB), 1u << 20)), dim3(TB), 0, ix->stream, tab, entries, f.pre5);
-    DG_HIP(hipStreamSynchronize(ix->stream));
-    DG_HIP(hipGetLastError());
+    DG_TRY(stage_table_pack(ix, t));
     pc.lap("table entries packed");
   }
-  // block minima over the suffix array for the top-k locate (0.57 n bytes; one streaming pass over SA)
-  f.samin[0] = sa;
+  f.samin[0] = f.sa;
   f.nlev = 1;
   if (!exp_env("DICEY_NO_SA_MINIMA")) {
-    u64 cnt = n;
-    const u32* prev = sa;
-    while (cnt > 8 && f.nlev < FmView::MAXLEV) {
-      const u64 nout = (cnt + 7) / 8, npad = ((nout + 7) & ~7ULL) + 8;
-      u32* lv = nullptr;
-      DG_HIP(big_alloc((void**)&lv, npad * 4, ix->stream));
-      ix->owned.push_back(lv);
-      ix->hbm_bytes += npad * 4;
-      hipLaunchKernelGGL(k_block_min8, dim3(ceil_div(npad, TB)), dim3(TB), 0, ix->stream, prev, cnt, lv, nout, npad);
-      f.samin[f.nlev++] = lv;
-      prev = lv;
-      cnt = nout;
-    }
-    DG_HIP(hipStreamSynchronize(ix->stream));
-    DG_HIP(hipGetLastError());
+    DG_TRY(stage_block_minima(ix));
     pc.lap("suffix-array block minima");
   }
   if (!(flags & DG_OPEN_NO_SELFCHECK)) {
-    DG_HIP(hipMalloc((void**)&bad, 4));
-    DG_HIP(hipMemsetAsync(bad, 0, 4, ix->stream));
-    u64 ns = n < (1u << 20) ? n : (1u << 20);
-    hipLaunchKernelGGL(k_selfcheck, dim3(ceil_div(ns, TB)), dim3(TB), 0, ix->stream, f, ns, bad);
-    u32 hbad = 0;
-    DG_HIP(hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, ix->stream));
-    DG_HIP(hipStreamSynchronize(ix->stream));
-    DG_HIP(hipFree(bad));
-    if (hbad) return fail(DG_EFORMAT, "index self-check failed on %u of %llu sampled suffixes", hbad, (unsigned long long)ns);
+    DG_TRY(stage_selfcheck(ix));
     pc.lap("self-check");
   }
-  ix->hbm_bytes += nblk * sizeof(OccBlock) + n + 64 + n * 4 + 64;
   return DG_OK;
 }
 
 template <class T>
 static int upload(dg_index* ix, const void* src, size_t bytes, const T** dst) {
   void* d = nullptr;
-  DG_HIP(big_alloc(&d, bytes + 64, ix->stream));  // +64: packed_get may touch one word past the last element
-  ix->owned.push_back(d);
+  DG_TRY(ix->own(&d, bytes + 64));  // +64: packed_get may touch one word past the last element
   DG_HIP(hipMemsetAsync((char*)d + bytes, 0, 64, ix->stream));
   DG_HIP(hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, ix->stream));
-  ix->hbm_bytes += bytes + 64;
   *dst = (const T*)d;
   return DG_OK;
 }
@@ -858,8 +868,8 @@ static int open_impl(const char* path, int device, u32 flags, dg_index* ix) {
   f.samp_width = c.sa_samples.width;
   f.n_sa_samp = c.sa_samples.bits / c.sa_samples.width;
   f.n_isa_samp = c.isa_samples.bits / c.isa_samples.width;
-  WtTables* t = new WtTables;
-  std::memset(t, 0, sizeof *t);
+  auto t = std::make_unique<WtTables>();
+  std::memset(t.get(), 0, sizeof *t);
   for (size_t v = 0; v < c.nodes.size(); ++v) {
     t->node_pos[v] = c.nodes[v].bv_pos;
     t->node_rank[v] = c.nodes[v].bv_pos_rank;
@@ -872,15 +882,11 @@ static int open_impl(const char* path, int device, u32 flags, dg_index* ix) {
   std::memcpy(t->char2comp, c.char2comp, 256);
   for (size_t i = 0; i < c.comp2char.size(); ++i) t->comp2char[i] = c.comp2char[i];
   t->sigma = c.sigma;
-  int rc = upload(ix, t, sizeof *t, &f.wt);
   for (int b = 0; b < 256; ++b) ix->code_len[b] = (c.c_to_leaf[b] == 0xFFFF) ? 0u : (u32)(c.path[b] >> 56);
   ix->sigma = c.sigma;
-  if (rc != DG_OK) {
-    delete t;
-    return rc;
-  }
-  DG_HIP(hipStreamSynchronize(ix->stream));
-  delete t;
+  DG_TRY(upload(ix, t.get(), sizeof *t, &f.wt));
+  DG_HIP(hipStreamSynchronize(ix->stream));  // the copy has read *t
+  t.reset();
   pc.lap("upload of the sdsl sections");
   static const u8 soc[8] = {'A', 'C', 'G', 'T', 'N', '\n', 0, 0};
   std::memcpy(f.sym_of_code, soc, 8);

@@ -39,6 +39,25 @@ struct dg_index {
   uint32_t code_len[256] = {0};
   uint64_t file_bytes = 0, hbm_bytes = 0;
   double load_seconds = 0, derive_seconds = 0;
+  // The one place where a device block becomes the index's: released by ~dg_index on `stream`, counted in hbm_bytes.
+  void adopt(void* p, size_t bytes) {  // a block a stage made complete before it handed it over (index.hip: a prefix level)
+    owned.push_back(p);
+    hbm_bytes += bytes;
+  }
+  int own(void** p, size_t bytes) {
+    DG_HIP(dg::big_alloc(p, bytes, stream));
+    adopt(*p, bytes);
+    return DG_OK;
+  }
+  bool try_own(void** p, size_t bytes) {  // the optional blocks: false, *p null and HIP's sticky error cleared when there is no room
+    if (dg::big_alloc(p, bytes, stream) == hipSuccess) {
+      adopt(*p, bytes);
+      return true;
+    }
+    (void)hipGetLastError();
+    *p = nullptr;
+    return false;
+  }
   // grow-only batch workspaces (see hunt.hip / seam.hip for the slot meaning)
   dg::DevBuf ws[dg::WS_COUNT];
   hipEvent_t ev[dg::EV_COUNT] = {nullptr};

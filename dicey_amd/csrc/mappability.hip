@@ -31,6 +31,7 @@
 #include <utility>
 #include <vector>
 
+#include "dev_mem.hpp"  // StreamScratch: the transient device buffers of one call
 #include "devfm.hpp"
 #include "experiments.hpp"
 #include "index_internal.hpp"
@@ -185,31 +186,6 @@ static void with_mismatches(u32 e, F&& f) {
   else f(std::integral_constant<int, 2>{});
 }
 
-// the transient device buffers of one call: released on its stream, in the order they were made, when the call returns
-struct Scratch {
-  hipStream_t st;
-  std::vector<std::pair<void*, bool>> made;  // (block, from big_alloc)
-  explicit Scratch(hipStream_t s) : st(s) {}
-  ~Scratch() {
-    (void)hipStreamSynchronize(st);
-    for (const auto& b : made) {
-      if (b.second) big_free(b.first, st);
-      else (void)hipFree(b.first);
-    }
-    (void)hipStreamSynchronize(st);
-  }
-  int big(void** p, size_t bytes) {
-    DG_HIP(big_alloc(p, bytes, st));
-    made.emplace_back(*p, true);
-    return DG_OK;
-  }
-  int small(void** p, size_t bytes) {
-    DG_HIP(hipMalloc(p, bytes));
-    made.emplace_back(*p, false);
-    return DG_OK;
-  }
-};
-
 // the events of a call with N phases, one of them a chunked search: N + 1 events around the phases and, with DICEY_TIMING, one in front of
 // every launch of the search, for the longest one.  Every event is owned from the moment it exists: a failed creation releases the others
 template <int N>
@@ -268,7 +244,7 @@ static int map_impl(dg_index* ix, const dg_map_params* prm, u32 mismatches, dg_m
   if ((u64)free_b < need + (64ULL << 20))
     return fail(DG_ENOMEM, "dg_mappability: needs %llu MB of device memory, %llu MB free", (unsigned long long)(need >> 20),
                 (unsigned long long)(free_b >> 20));
-  Scratch b(st);
+  StreamScratch b(st);
   void *b_start = nullptr, *b_bm = nullptr, *b_scan = nullptr, *b_steps = nullptr;
   DG_HIP(big_alloc((void**)&m->out, n * 4 + 256, st));
   DG_TRY(b.big(&b_start, n * 4 + 256));
@@ -363,7 +339,7 @@ static int min_unique_impl(dg_index* ix, u32 max_k, int forward_only, dg_map* m)
   if ((u64)free_b < need + (64ULL << 20))
     return fail(DG_ENOMEM, "dg_min_unique: needs %llu MB of device memory, %llu MB free", (unsigned long long)(need >> 20),
                 (unsigned long long)(free_b >> 20));
-  Scratch b(st);
+  StreamScratch b(st);
   void *b_lcp = nullptr, *b_steps = nullptr;
   DG_HIP(big_alloc((void**)&m->out, n * 4 + 256, st));
   DG_TRY(b.big(&b_lcp, lcp_bytes));
@@ -454,7 +430,7 @@ static int query_args_check(const char* who, dg_index* ix, const uint8_t* seqs, 
 // of nw words each (the A/C/G/T bitmap first, the valid bitmap second) and a counter record.  alloc() checks the free memory and allocates
 // everything; upload() queues the copy and k_acgt_bits or, for records with IUPAC codes, k_iupac_bits.
 struct QueryDev {
-  Scratch mem;
+  StreamScratch mem;
   u64 qn = 0, nw_data = 0, nw = 0, q_bytes = 0;
   void *q = nullptr, *out = nullptr, *bm = nullptr, *ctr = nullptr;
   explicit QueryDev(hipStream_t s) : mem(s) {}
