@@ -168,7 +168,7 @@ class FmIndex:
         times and, for e > 0, the search counters (dg_map_mm_stats_t)."""
         return self._map_array(self._map(k, forward_only, max_count, mismatches), stats, mm=mismatches > 0)
 
-    def _map_array(self, m, stats, mm=False):
+    def _map_array(self, m, stats, mm=False, mu_mm=False):
         """the values of a dg_map as a numpy array (and its stats into `stats`); frees the map"""
         import numpy as np
         try:
@@ -182,6 +182,10 @@ class FmIndex:
                     ms = _capi.MapMmStats()
                     _capi.check(self._L, self._L.dg_map_mm_stats(m, C.byref(ms)))
                     stats.update({f: getattr(ms, f) for f, _ in _capi.MapMmStats._fields_})
+                if mu_mm:
+                    us = _capi.MuMmStats()
+                    _capi.check(self._L, self._L.dg_map_mu_mm_stats(m, C.byref(us)))
+                    stats.update({f: getattr(us, f) for f, _ in _capi.MuMmStats._fields_})
             return out
         finally:
             self._L.dg_map_free(m)
@@ -200,23 +204,30 @@ class FmIndex:
         finally:
             self._L.dg_map_free(m)
 
-    def _min_unique(self, max_k, forward_only):
+    def _min_unique(self, max_k, forward_only, mismatches=0):
         m = C.c_void_p()
-        prm = _capi.MinUniqueParams(max_k, 1 if forward_only else 0, 0, 0)
-        _capi.check(self._L, self._L.dg_min_unique(self._h, C.byref(prm), C.byref(m)))
+        if mismatches == 0:
+            prm = _capi.MinUniqueParams(max_k, 1 if forward_only else 0, 0, 0)
+            _capi.check(self._L, self._L.dg_min_unique(self._h, C.byref(prm), C.byref(m)))
+        else:
+            prm = _capi.MinUniqueMmParams(max_k, mismatches, 1 if forward_only else 0, 0, 0)
+            _capi.check(self._L, self._L.dg_min_unique_mm(self._h, C.byref(prm), C.byref(m)))
         return m
 
-    def min_unique(self, max_k: int = 100, forward_only: bool = False, stats: Optional[dict] = None):
+    def min_unique(self, max_k: int = 100, forward_only: bool = False, stats: Optional[dict] = None, mismatches: int = 0):
         """Minimum unique length of every text position (include/dicey_gpu.h dg_min_unique): numpy uint32 array of n-1 values,
         value[p] = the smallest k <= min(run of A/C/G/T from p, max_k) at which mappability(k)[p] == 1 (with forward_only: at which
         the k-mer occurs once on the forward strand), 0 where there is none.  `stats`, when given, receives dg_map_stats_t: the
-        neighbour-prefix pass in ms_forward, the other strand's backward search in ms_reverse and its steps in rev_steps."""
-        return self._map_array(self._min_unique(max_k, forward_only), stats)
+        neighbour-prefix pass in ms_forward, the other strand's backward search in ms_reverse and its steps in rev_steps.
+        With mismatches = e in 1..2 (dg_min_unique_mm) a length is unique when no other k-mer of the genome, and no k-mer of its
+        other strand, is within e substitutions: the smallest k at which mappability(k, mismatches=e)[p] == 1.  `stats` then also
+        receives the search counters (dg_mu_mm_stats_t), and ms_total includes their ms_search."""
+        return self._map_array(self._min_unique(max_k, forward_only, mismatches), stats, mu_mm=mismatches > 0)
 
-    def min_unique_runs(self, max_k: int = 100, forward_only: bool = False, lo: int = 0, hi: Optional[int] = None):
+    def min_unique_runs(self, max_k: int = 100, forward_only: bool = False, lo: int = 0, hi: Optional[int] = None, mismatches: int = 0):
         """The same lengths as maximal runs of equal non-zero values inside text positions [lo, hi) (hi = n-1 when None): numpy
         arrays (start uint64, length uint32, value uint32); a run is cut at lo and hi."""
-        m = self._min_unique(max_k, forward_only)
+        m = self._min_unique(max_k, forward_only, mismatches)
         try:
             if hi is None:
                 st = _capi.MapStats()

@@ -150,6 +150,16 @@ class MinUniqueParams(C.Structure):
     _fields_ = [("max_k", C.c_uint32), ("forward_only", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class MinUniqueMmParams(C.Structure):
+    _fields_ = [("max_k", C.c_uint32), ("mismatches", C.c_uint32), ("forward_only", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class MuMmStats(C.Structure):
+    _fields_ = [("candidates", C.c_uint64), ("probes", C.c_uint64), ("steps", C.c_uint64), ("table_reads", C.c_uint64),
+                ("verified_rows", C.c_uint64), ("launches", C.c_uint64), ("ms_search", C.c_double)]
+
+
 # every symbol include/dicey_gpu.h declares; tests/test_capi_symbols.py checks the list against the header
 class PadlockParams(C.Structure):
     _fields_ = [("armlen", C.c_uint32), ("distance", C.c_uint32), ("hamming", C.c_int32), ("tmdiff", C.c_uint32),
@@ -172,7 +182,7 @@ SYMBOLS = ["dg_index_open", "dg_index_close", "dg_index_stats", "dg_count", "dg_
            "dg_chit_unpack", "dg_normalize_query", "dg_hunt_expand", "dg_index_stream", "dg_fm9_check",
            "dg_mappability", "dg_map_values", "dg_map_runs", "dg_map_device_values", "dg_map_stats", "dg_map_free",
            "dg_mappability_mm", "dg_map_mm_stats", "dg_min_unique", "dg_query_map", "dg_query_min_len",
-           "dg_query_map_anchored", "dg_query_min_len_end", "dg_query_map_iupac"]
+           "dg_query_map_anchored", "dg_query_min_len_end", "dg_query_map_iupac", "dg_min_unique_mm", "dg_map_mu_mm_stats"]
 
 _lib = None
 
@@ -249,6 +259,8 @@ def load(path=None):
     L.dg_mappability_mm.argtypes = [vp, C.POINTER(MapMmParams), C.POINTER(vp)]
     L.dg_map_mm_stats.argtypes = [vp, C.POINTER(MapMmStats)]
     L.dg_min_unique.argtypes = [vp, C.POINTER(MinUniqueParams), C.POINTER(vp)]
+    L.dg_min_unique_mm.argtypes = [vp, C.POINTER(MinUniqueMmParams), C.POINTER(vp)]
+    L.dg_map_mu_mm_stats.argtypes = [vp, C.POINTER(MuMmStats)]
     L.dg_query_map.argtypes = [vp, C.POINTER(QmapParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapStats)]
     L.dg_query_min_len.argtypes = [vp, C.POINTER(QminlenParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QminlenStats)]
     L.dg_query_map_anchored.argtypes = [vp, C.POINTER(QmapAnchorParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapStats)]

@@ -3,6 +3,7 @@
 // starts there, on both strands, counted on the FM-index in HBM.  The device hands over runs of equal values per position chunk;
 // the host formats the chunks on several threads, compresses them (-o) into concatenated gzip members and writes them in order.
 // With -u the value is the minimum unique length instead (dg_min_unique): the shortest k-mer that starts at the position and is unique.
+// With -u -w the length must be unique within -w mismatches, on both strands (dg_min_unique_mm).
 // With -q the positions are those of the records of a second FASTA file, which need not be in the genome (dg_query_map): zero is a value there.
 // With -q -l the value is the query minimum length (dg_query_min_len): the shortest k-mer from the position with at most -t places in the genome.
 // With -q -a the last -a bases of every k-mer, the oligo's 3' end, must match exactly (dg_query_map_anchored).
@@ -28,7 +29,8 @@ const OptSpec kMapOpts[] = {{"help", '?', false},  {"genome", 'g', true},  {"kme
                             {"mismatches", 'e', true}, {"minunique", 'u', false},
                             {"query", 'q', true}, {"minlength", 'l', false}, {"shortest", 's', true},
                             {"atmost", 't', true}, {"anchor", 'a', true},
-                            {"byend", 'E', false}, {"iupac", 'I', false}, {"maxdegeneracy", 'D', true}};
+                            {"byend", 'E', false}, {"iupac", 'I', false}, {"maxdegeneracy", 'D', true},
+                            {"within", 'w', true}};
 
 void map_usage() {
   std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz [-q targets.fa.gz]" << std::endl;
@@ -40,6 +42,8 @@ void map_usage() {
                "  -f [ --forward ]                   forward strand only\n"
                "  -c [ --maxcount ] arg (=0)         write min(value, maxcount); 0 = exact values\n"
                "  -u [ --minunique ]                 write the minimum unique length instead; -k is then the largest length tried\n"
+               "  -w [ --within ] arg (=0)           with -u: a length is unique when no other k-mer of the genome, and no k-mer of its other\n"
+               "                                     strand, is within arg mismatches (0..2)\n"
                "  -q [ --query ] arg                 FASTA file of sequences to rate against the genome instead of the genome itself\n"
                "  -l [ --minlength ]                 with -q: write the shortest specific length instead; -k is then the largest length tried\n"
                "  -s [ --shortest ] arg (=10)        with -l: the smallest length tried (10..1000, at most -k)\n"
@@ -59,6 +63,10 @@ void map_usage() {
                "With -u the value of a position is the smallest length k (at most -k, and inside the run of A/C/G/T that starts there) at\n"
                "which the k-mer that starts there has value 1: it occurs once and its reverse complement nowhere (-f: once on the forward\n"
                "strand).  Positions without such a length, still repeated at -k or at the end of their run, have no line.\n"
+               "With -u -w 1 or -w 2 a length counts as unique only when the k-mer that starts there is the one k-mer of the genome within that\n"
+               "many mismatches (substitutions) of itself and of its reverse complement: the smallest k at which -e with the same number writes 1,\n"
+               "for every k at once.  The lengths are never below those of -u alone, and a k-mer within -w mismatches of its own reverse\n"
+               "complement is not unique at that length unless -f is given.  -w 0 writes what -u writes.\n"
                "With -q the lines are those of the records of the query file (upper-cased; the name is the header's first word), in file\n"
                "order: the value of a position is the number of k-mers of the GENOME within -e mismatches of the record's k-mer and of its\n"
                "reverse complement.  The sequences need not be in the genome, so 0 is a value (absent from the genome) and has lines of\n"
@@ -239,8 +247,8 @@ int mappability_main(int argc, char** argv) {
   }
   std::string genome, outfile, query;
   bool help = false, have_genome = false, forward = false, minunique = false, have_query = false, minlength = false, have_shortest = false,
-       have_atmost = false, have_anchor = false, byend = false, iupac = false, have_maxdeg = false;
-  long long k = 100, maxcount = 0, mismatches = 0, shortest = 10, atmost = 0, anchor = 0, maxdeg = 256;
+       have_atmost = false, have_anchor = false, byend = false, iupac = false, have_maxdeg = false, have_within = false;
+  long long k = 100, maxcount = 0, mismatches = 0, shortest = 10, atmost = 0, anchor = 0, maxdeg = 256, within = 0;
   for (auto& kv : p.kv) {
     if (kv.first == "help") help = true;
     else if (kv.first == "genome") { genome = kv.second; have_genome = true; }
@@ -258,6 +266,7 @@ int mappability_main(int argc, char** argv) {
     else if (kv.first == "byend") byend = true;
     else if (kv.first == "iupac") iupac = true;
     else if (kv.first == "maxdegeneracy") { maxdeg = std::strtoll(kv.second.c_str(), nullptr, 10); have_maxdeg = true; }
+    else if (kv.first == "within") { within = std::strtoll(kv.second.c_str(), nullptr, 10); have_within = true; }
   }
   if (help || !have_genome || !p.positional.empty()) {
     map_usage();
@@ -284,6 +293,8 @@ int mappability_main(int argc, char** argv) {
   if (have_maxdeg && !iupac) return bail("Error: --maxdegeneracy needs --iupac!");
   if (iupac && k > 64) return bail("Error: k-mer length " + std::to_string(k) + " outside 10..64 (--iupac)!");
   if (maxdeg < 1 || maxdeg > 4096) return bail("Error: maxdegeneracy " + std::to_string(maxdeg) + " outside 1..4096!");
+  if (have_within && !minunique) return bail("Error: --within needs --minunique!");
+  if (within < 0 || within > 2) return bail("Error: within " + std::to_string(within) + " outside 0..2!");
   if (!file_nonempty(genome)) return bail("Error: Genome does not exist!");
   if (have_query && !file_nonempty(query)) return bail("Error: Query file " + query + " does not exist or is empty!");
   if (byend && !minlength) return bail("Error: --byend needs --minlength!");
@@ -322,8 +333,10 @@ int mappability_main(int argc, char** argv) {
   }
   dg_map_mm_params mp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, 0u};
   dg_min_unique_params up = {(uint32_t)k, forward ? 1 : 0, 0u, 0u};
+  dg_min_unique_mm_params wp = {(uint32_t)k, (uint32_t)within, forward ? 1 : 0, 0u, 0u};
   dg_map* m = nullptr;
-  if ((minunique ? dg_min_unique(ix, &up, &m) : dg_mappability_mm(ix, &mp, &m)) != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
+  if ((minunique ? (within ? dg_min_unique_mm(ix, &wp, &m) : dg_min_unique(ix, &up, &m)) : dg_mappability_mm(ix, &mp, &m)) != DG_OK)
+    return bail(std::string("dicey: ") + dg_last_error());
   struct MapFreer {
     dg_map* m;
     ~MapFreer() { dg_map_free(m); }

@@ -14,9 +14,10 @@
 //   hunt.hip      DICEY_NO_BAND_VERIFY DICEY_CAP_HOST DICEY_NO_FUSED_SELECT DICEY_NO_FUSED_SELECT2 DICEY_NO_PREP_FUSION DICEY_NO_PRE5_D2
 //                 DICEY_NO_FLAT_HAMMING2 DICEY_NO_N_WINDOW DICEY_NO_LONG2 DICEY_NO_DIRECT_CTX DICEY_DEBUG_CAPS DICEY_FUSED_LCAP DICEY_VERIFY_CH DICEY_DUMP_JOBS DICEY_EXP
 //   index.hip     DICEY_NO_KMER_FILTER DICEY_NO_NRUN_PRUNE DICEY_NO_PRE5 DICEY_NO_SAX DICEY_NO_PLV DICEY_NO_SA_MINIMA DICEY_EXP_PRIO
-//   mappability.hip   DICEY_MAP_CHUNK (positions per dg_map_runs pass) DICEY_MAP_HEAD_CHUNK (ranks per launch of the e >= 1 search and of dg_min_unique)
+//   mappability.hip   DICEY_MAP_CHUNK (positions per dg_map_runs pass) DICEY_MAP_HEAD_CHUNK (ranks per launch of the e >= 1 search, of dg_min_unique and of dg_min_unique_mm)
 //                 DICEY_MAP_NARROW (W: intervals of at most W rows are verified on the text; 0 = never) DICEY_QMAP_CHUNK (positions per launch
-//                 of dg_query_map) DICEY_QMINLEN_CHUNK (positions per launch of dg_query_min_len) -- results do not depend on them
+//                 of dg_query_map) DICEY_QMINLEN_CHUNK (positions per launch of dg_query_min_len) DICEY_MU_MM_RANK_ORDER (dg_min_unique_mm: lanes by rank
+//                 instead of by text position) -- results do not depend on them
 //   search.hip / thal_api.hip   DICEY_NO_LDS_TABLES DICEY_NO_WAVE_THAL DICEY_DEBUG_THAL_REDO DICEY_DEBUG_DUMP_RAW
 #pragma once
 #include <cstdlib>

@@ -14,7 +14,8 @@
 // per group head a backward search with a mismatch budget of w and of revcomp(w), launched per chunk of head ranks.
 // Transient HBM: the start array (4n) and three bitmaps (3n/8) beside the result (4n), which the end scan uses first.
 // dg_min_unique (min_unique.hpp) answers the inverse question on the same handle type: per position the smallest k at which the value
-// is 1, from one pass over neighbouring suffixes and one backward search per rank.
+// is 1, from one pass over neighbouring suffixes and one backward search per rank.  dg_min_unique_mm (min_unique_mm.hpp) asks the same
+// with up to two mismatches: the two exact passes, then one lane per position that probes lengths from the exact answer upward.
 // dg_query_map (query_map.hpp) runs phase 1 on a buffer of query records laid out like the text and then one search per valid position
 // of it: the (k,e) counts of k-mers that are not in the index.  dg_query_min_len (query_min_len.hpp) looks, on the same buffer, for the
 // smallest k at which that count is at most t.  dg_query_map_anchored (query_anchor.hpp) is dg_query_map with the last a bases of every
@@ -37,6 +38,7 @@
 #include "index_internal.hpp"
 #include "map_mm.hpp"           // k_heads' sibling for e >= 1 mismatches
 #include "min_unique.hpp"         // the kernels of dg_min_unique
+#include "min_unique_mm.hpp"      // and the search with a mismatch budget on top of them (dg_min_unique_mm)
 #include "query_anchor.hpp"       // k_qmap with the k-mer's last bases matched exactly (dg_query_map_anchored)
 #include "query_iupac.hpp"        // k_qmap_anch for k-mers with IUPAC codes, one search per expansion (dg_query_map_iupac)
 #include "query_map.hpp"          // the same search per position of a query buffer (dg_query_map)
@@ -51,6 +53,7 @@ struct dg_map {
   uint32_t* out = nullptr;       // u32[n] (the entry at n-1, the sentinel, is 0)
   dg_map_stats_t st{};
   dg_map_mm_stats_t mm{};  // all zero for an exact map
+  dg_mu_mm_stats_t mu{};   // all zero unless dg_min_unique_mm searched with mismatches
   dg::DevBuf run_flags, run_pos, run_val, run_cnt;  // dg_map_runs workspaces (grow-only)
   ~dg_map() {
     (void)hipSetDevice(device);
@@ -325,8 +328,14 @@ static int map_impl(dg_index* ix, const dg_map_params* prm, u32 mismatches, dg_m
 
 // default ranks per launch of the two passes (the same reasoning as MM_HEAD_CHUNK: no launch holds a shared device for long)
 static constexpr u64 MU_CHUNK = 1ULL << 24;
+// default positions per k_mu_mm launch at e = 2, where a lane runs 5 to 7 searches of 1 + 3K + 9K(K-1)/2 table reads each: a launch of 2^24
+// takes 9 to 19 s on the 64 Mb genomes.  e = 1 keeps 2^24 (0.3 to 0.7 s): shorter launches cost more than they give, each one waits for
+// its slowest workgroup (DESIGN.md §10 has the measurements)
+static constexpr u64 MU_MM_CHUNK2 = 1ULL << 22;
 
-static int min_unique_impl(dg_index* ix, u32 max_k, int forward_only, dg_map* m) {
+// who: the entry point's name for messages.  mismatches = 0: the two exact passes (dg_min_unique).  e = 1, 2: k_mu_mm behind them, positions in
+// chunks of launches; it reads mul_0 from the result array and overwrites it, and kernel boundaries separate the passes
+static int min_unique_impl(const char* who, dg_index* ix, u32 max_k, int forward_only, u32 mismatches, dg_map* m) {
   const FmView& f = ix->view;
   const u64 n = f.n;
   // the INDEX handle's stream, as map_impl: the passes read the index and are ordered with the handle's other work; the map's own stream
@@ -337,19 +346,26 @@ static int min_unique_impl(dg_index* ix, u32 max_k, int forward_only, dg_map* m)
   size_t free_b = 0, total_b = 0;
   DG_HIP(hipMemGetInfo(&free_b, &total_b));
   if ((u64)free_b < need + (64ULL << 20))
-    return fail(DG_ENOMEM, "dg_min_unique: needs %llu MB of device memory, %llu MB free", (unsigned long long)(need >> 20),
+    return fail(DG_ENOMEM, "%s: needs %llu MB of device memory, %llu MB free", who, (unsigned long long)(need >> 20),
                 (unsigned long long)(free_b >> 20));
   StreamScratch b(st);
-  void *b_lcp = nullptr, *b_steps = nullptr;
+  void *b_lcp = nullptr, *b_steps = nullptr, *b_mm = nullptr;
   DG_HIP(big_alloc((void**)&m->out, n * 4 + 256, st));
   DG_TRY(b.big(&b_lcp, lcp_bytes));
   DG_TRY(b.small(&b_steps, 8));
-  u64 chunk = MU_CHUNK;
-  if (const char* e = exp_env("DICEY_MAP_HEAD_CHUNK")) chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
+  if (mismatches) DG_TRY(b.small(&b_mm, sizeof(MuMmCounters)));
+  u64 chunk = MU_CHUNK, mm_chunk = mismatches >= 2 ? MU_MM_CHUNK2 : MU_CHUNK;
+  u32 W = MM_NARROW;
+  if (const char* e = exp_env("DICEY_MAP_HEAD_CHUNK")) chunk = mm_chunk = std::max<u64>(1, std::strtoull(e, nullptr, 10));
+  if (const char* e = exp_env("DICEY_MAP_NARROW")) W = (u32)std::min<u64>(std::strtoull(e, nullptr, 10), 0xFFFFFFFFull);
   ChunkTimer<2> tm;  // forward (k_mu_lcp) | reverse (the chunked walk)
   DG_TRY(tm.init());
+  const int rank_order = exp_env("DICEY_MU_MM_RANK_ORDER") != nullptr;  // lanes by rank instead of by text position (a measurement aid)
+  ChunkTimer<1> ts;  // the chunked search with mismatches behind them
+  if (mismatches) DG_TRY(ts.init());
   const u32 TB = 256;
   DG_HIP(hipMemsetAsync(b_steps, 0, 8, st));
+  if (mismatches) DG_HIP(hipMemsetAsync(b_mm, 0, sizeof(MuMmCounters), st));
   DG_HIP(hipEventRecord(tm.ev[0], st));
   for (u64 r0 = 0; r0 < n + 1; r0 += chunk) {  // ranks 0..n: lcp[n] closes the array
     const u64 r1 = std::min(n + 1, r0 + chunk);
@@ -364,6 +380,22 @@ static int min_unique_impl(dg_index* ix, u32 max_k, int forward_only, dg_map* m)
                        (unsigned long long*)b_steps);
   }
   DG_HIP(hipEventRecord(tm.ev[2], st));
+  u64 mm_launches = 0;
+  MuMmCounters hc{};
+  if (mismatches) {
+    DG_HIP(hipEventRecord(ts.ev[0], st));
+    for (u64 r0 = 0; r0 < n; r0 += mm_chunk, ++mm_launches) {
+      const u64 r1 = std::min(n, r0 + mm_chunk);
+      DG_TRY(ts.launch(st));
+      with_mismatches(mismatches, [&](auto E) {
+        if constexpr (E.value > 0)  // (e = 0 ends with the walk above)
+          hipLaunchKernelGGL(k_mu_mm<E.value>, dim3(ceil_div(r1 - r0, TB)), dim3(TB), 0, st, f, max_k, forward_only, W, rank_order, r0, r1,
+                             m->out, (MuMmCounters*)b_mm);
+      });
+    }
+    DG_HIP(hipEventRecord(ts.ev[1], st));
+    DG_HIP(hipMemcpyAsync(&hc, b_mm, sizeof hc, hipMemcpyDeviceToHost, st));
+  }
   DG_HIP(hipMemcpyAsync(&m->st.rev_steps, b_steps, 8, hipMemcpyDeviceToHost, st));
   DG_HIP(hipStreamSynchronize(st));
   DG_HIP(hipGetLastError());
@@ -378,6 +410,21 @@ static int min_unique_impl(dg_index* ix, u32 max_k, int forward_only, dg_map* m)
   if (tm.timing && launches)
     std::fprintf(stderr, "dicey timing: min unique max_k=%u: %llu launches of the walk, %.1f ms in all, longest %.1f ms\n", max_k,
                  (unsigned long long)launches, ms[1], longest);
+  if (mismatches) {
+    float mss[1] = {0}, mm_longest = 0;
+    DG_TRY(ts.read(mss, 0, &mm_longest));
+    m->mu.candidates = hc.candidates;
+    m->mu.probes = hc.probes;
+    m->mu.steps = hc.steps;
+    m->mu.table_reads = hc.table_reads;
+    m->mu.verified_rows = hc.verified_rows;
+    m->mu.launches = mm_launches;
+    m->mu.ms_search = mss[0];
+    m->st.ms_total = (double)ms[0] + (double)ms[1] + (double)mss[0];  // in double: exactly ms_forward + ms_reverse + ms_search
+    if (ts.timing && mm_launches)
+      std::fprintf(stderr, "dicey timing: min unique max_k=%u e=%u: %llu launches of the search, %.1f ms in all, longest %.1f ms\n", max_k, mismatches,
+                   (unsigned long long)mm_launches, mss[0], mm_longest);
+  }
   return DG_OK;
 }
 
@@ -625,9 +672,9 @@ using namespace dg;
 
 extern "C" {
 
-// mode: 0 = dg_mappability / dg_mappability_mm (p->k is k), 1 = dg_min_unique (p->k is max_k)
+// mode: 0 = dg_mappability / dg_mappability_mm (p->k is k), 1 = dg_min_unique, 2 = dg_min_unique_mm (p->k is max_k)
 static int map_open(dg_index* ix, const dg_map_params* p, u32 mismatches, int mode, dg_map** out) {
-  const char* who = mode ? "dg_min_unique" : "dg_mappability";
+  const char* who = mode == 2 ? "dg_min_unique_mm" : mode ? "dg_min_unique" : "dg_mappability";
   if (p->k < 10 || p->k > 1000) return fail(DG_ELIMIT, "%s: %s = %u outside 10..1000", who, mode ? "max_k" : "k", p->k);
   if (ix->view.n < 2 || ix->view.n > 0xFFFFFFFFull) return fail(DG_ELIMIT, "%s: index of %llu suffixes", who, (unsigned long long)ix->view.n);
   if (ix->any_lane_busy()) return fail(DG_EINVAL, "%s: a dg_hunt_submit batch is in flight on this handle (dg_hunt_wait first)", who);
@@ -641,7 +688,7 @@ static int map_open(dg_index* ix, const dg_map_params* p, u32 mismatches, int mo
     delete m;
     return fail(DG_EHIP, "%s: cannot create a stream", who);
   }
-  const int rc = mode ? min_unique_impl(ix, p->k, p->forward_only, m) : map_impl(ix, p, mismatches, m);
+  const int rc = mode ? min_unique_impl(who, ix, p->k, p->forward_only, mismatches, m) : map_impl(ix, p, mismatches, m);
   if (rc != DG_OK) {
     delete m;
     return rc;
@@ -675,6 +722,17 @@ int dg_min_unique(dg_index* ix, const dg_min_unique_params* p, dg_map** out) {
   if (!ix) return fail(DG_EINVAL, "dg_min_unique: null argument");
   const dg_map_params q = {p->max_k, p->forward_only, 0u, 0u};
   return map_open(ix, &q, 0, 1, out);
+}
+
+int dg_min_unique_mm(dg_index* ix, const dg_min_unique_mm_params* p, dg_map** out) {
+  if (out) *out = nullptr;
+  if (!p || !out) return fail(DG_EINVAL, "dg_min_unique_mm: null argument");
+  if (p->flags || p->reserved) return fail(DG_EINVAL, "dg_min_unique_mm: flags and reserved must be 0");
+  if (p->max_k < 10 || p->max_k > 1000) return fail(DG_ELIMIT, "dg_min_unique_mm: max_k = %u outside 10..1000", p->max_k);
+  if (p->mismatches > 2) return fail(DG_ELIMIT, "dg_min_unique_mm: %u mismatches outside 0..2", p->mismatches);
+  if (!ix) return fail(DG_EINVAL, "dg_min_unique_mm: null argument");
+  const dg_map_params q = {p->max_k, p->forward_only, 0u, 0u};
+  return map_open(ix, &q, p->mismatches, 2, out);
 }
 
 int dg_query_map(dg_index* ix, const dg_qmap_params* p, const uint8_t* seqs, const uint64_t* off, size_t nseq, uint32_t* values,
@@ -753,6 +811,12 @@ int dg_query_min_len_end(dg_index* ix, const dg_qminlen_end_params* p, const uin
 int dg_map_mm_stats(const dg_map* m, dg_map_mm_stats_t* out) {
   if (!m || !out) return fail(DG_EINVAL, "dg_map_mm_stats: null argument");
   *out = m->mm;
+  return DG_OK;
+}
+
+int dg_map_mu_mm_stats(const dg_map* m, dg_mu_mm_stats_t* out) {
+  if (!m || !out) return fail(DG_EINVAL, "dg_map_mu_mm_stats: null argument");
+  *out = m->mu;
   return DG_OK;
 }
 

@@ -43,7 +43,8 @@ extern "C" {
  * 7 (additive exports, same version): dg_mappability_mm, dg_map_mm_stats ((k,e)-mappability, up to two mismatches)
  * 7 (additive exports, same version): dg_query_map (the same counts for the k-mers of sequences outside the index)
  * 7 (additive exports, same version): dg_min_unique (the shortest unique k-mer at each position)
- * 7 (additive exports, same version): dg_query_min_len (the shortest specific k-mer at each position of sequences outside the index) */
+ * 7 (additive exports, same version): dg_query_min_len (the shortest specific k-mer at each position of sequences outside the index)
+ * 7 (additive exports, same version): dg_min_unique_mm, dg_map_mu_mm_stats (the shortest k-mer unique within up to two mismatches) */
 #define DG_ABI_VERSION 7
 
 enum {
@@ -533,6 +534,48 @@ typedef struct {
 } dg_min_unique_params;
 int dg_min_unique(dg_index* ix, const dg_min_unique_params* p, dg_map** out);
 
+/* ABI 7, additive.  Minimum unique length with mismatches, (k,e)-mappability over all k at once: how long must an oligo that starts at p
+ * be before nothing else in the genome, on either strand, is within e substitutions of it?  T, run(p) and limit(p) as for dg_min_unique,
+ * e = mismatches in 0..2:
+ *   value_{e,k}(p) = what dg_mappability_mm writes at p for this k, e and forward_only with max_count = 0: the valid windows of the text
+ *                    within e substitutions of w_k = T[p, p+k) and of its reverse complement; w_k itself is one of them, so the value is
+ *                    >= 1 wherever k <= run(p),
+ *   mul_e(p)       = the smallest k in 1..limit(p) with value_{e,k}(p) == 1, and 0 when there is none.
+ * value_{e,k}(p) never rises with k on either strand (a window within e of the (k+1)-mer has its k-prefix within e of the k-mer; on the
+ * other strand the window one further right; a valid (k+1)-window has a valid k-prefix and k-suffix), so "value == 1" is false up to some
+ * k and true from there on.  Hence: mul_0 is dg_min_unique, bit for bit (mismatches = 0 IS that call); for every k in 10..max_k and every
+ * p valid at k, mul_e(p) != 0 && mul_e(p) <= k  <=>  dg_mappability_mm(k, e)[p] == 1; mul_e(p) is 0 or >= mul_{e-1}(p), and 0 wherever
+ * mul_{e-1}(p) is 0 (a window within e-1 is within e); and dg_query_min_len(min_k, max_k, at_most = 1, e) on a record equal to a whole
+ * sequence returns DG_QMAP_INVALID where limit(p) < min_k, 0 where mul_e(p) == 0 and max(mul_e(p), min_k) elsewhere.  A k-mer within e
+ * of its own reverse complement counts itself on the other strand and is never unique at that length unless forward_only is set.
+ * The call runs dg_min_unique's two passes and then one search per position with mul_0(p) != 0 that probes lengths from mul_0(p)
+ * upward (positions in chunks of launches); it needs dg_min_unique's memory, about 6n bytes of free HBM beside the index (DG_ENOMEM
+ * before any kernel otherwise).  The result is an ordinary dg_map: dg_map_values / dg_map_runs / dg_map_device_values / dg_map_free
+ * serve it; dg_map_stats has k = max_k, ms_forward and ms_reverse the two exact passes (rev_steps the steps of the second), ms_valid =
+ * ms_scatter = 0 and ms_total = ms_forward + ms_reverse + dg_mu_mm_stats_t::ms_search, formed in double in that order;
+ * dg_map_mm_stats stays all zero.  Checked in this order: a null parameter block or out pointer DG_EINVAL; non-zero flags or reserved
+ * DG_EINVAL; max_k outside 10..1000 or mismatches > 2 DG_ELIMIT; a null handle DG_EINVAL; free HBM (DG_ENOMEM); then DG_EINVAL while a
+ * dg_hunt_submit batch is in flight on the handle.  *out is cleared on every failure. */
+typedef struct {
+  uint32_t max_k;       /* 10..1000 */
+  uint32_t mismatches;  /* e: 0, 1 or 2 substitutions */
+  int32_t forward_only; /* the k-mer's own strand alone */
+  uint32_t flags;       /* 0 */
+  uint32_t reserved;    /* 0 */
+} dg_min_unique_mm_params;
+int dg_min_unique_mm(dg_index* ix, const dg_min_unique_mm_params* p, dg_map** out);
+/* counters of the search with mismatches (all zero for a map made with mismatches = 0 or by any other call) */
+typedef struct {
+  uint64_t candidates;    /* positions with mul_0(p) != 0: the ones searched */
+  uint64_t probes;        /* (position, k) pairs searched */
+  uint64_t steps;         /* backward-search steps (one pair of Occ lines each, all four characters) */
+  uint64_t table_reads;   /* K-mer table entries read */
+  uint64_t verified_rows; /* suffix-array rows finished on the text */
+  uint64_t launches;      /* kernel launches of the search (positions go through in chunks) */
+  double ms_search;       /* device time of the search, behind the two exact passes */
+} dg_mu_mm_stats_t;
+int dg_map_mu_mm_stats(const dg_map* m, dg_mu_mm_stats_t* out);
+
 /* ABI 7, additive.  Query mappability: the (k,e) counts of dg_mappability_mm for the k-mers of sequences that are NOT in the index (a
  * transcript across an exon-exon junction, a transgene, a viral genome, another allele).  Record i is seqs[off[i] .. off[i+1]), bytes
  * as given; empty records are allowed; values[off[i] + p] answers position p of record i.  For a record Q, a position p and e =
@@ -582,7 +625,7 @@ int dg_query_map(dg_index* ix, const dg_qmap_params* p, const uint8_t* seqs, con
  *   len(p)     = DG_QMAP_INVALID when limit(p) < min_k (no k-mer of the smallest length starts there), otherwise
  *                the smallest k in [min_k, limit(p)] with value_k(p) <= at_most, and 0 when there is none (still not specific at limit(p)).
  * at_most = 0 asks for "absent from the genome" (off-target design), at_most = 1 for "at most one place" (for a cut of the genome: unique,
- * with mismatches, which dg_min_unique does not offer).  value_k(p) never rises with k (a window within e of the (k+1)-mer has its
+ * with mismatches; dg_min_unique_mm answers that for the whole index text in one call).  value_k(p) never rises with k (a window within e of the (k+1)-mer has its
  * k-prefix within e of the k-mer; on the other strand the window one further right), so the device searches per position instead of
  * scanning every k: one call where a scan of dg_query_map needs max_k - min_k + 1.  Runs on the handle's stream, positions in chunks of
  * launches; needs the query bytes, 4 bytes per position and one bitmap of free HBM (DG_ENOMEM before any kernel otherwise).  nseq = 0

@@ -6,7 +6,10 @@ forward only; with --mismatches 1|2 the runs go through dg_mappability_mm ((k,e)
 dg_map_mm_stats per head.  With --min-unique [--maxk K] the runs go through dg_min_unique instead (the shortest unique k-mer per
 position): total, forward (neighbour prefixes) and reverse (the other strand's walk) ms, walk steps per position and, from the library's
 DICEY_TIMING line, the longest launch of the walk — and beside each, on the same genome and build, ONE exact dg_mappability pass at
-k = K: a bisection over 10..1000 needs seven of those.  With --query the runs go through dg_query_map (k-mer counts for sequences
+k = K: a bisection over 10..1000 needs seven of those.  With --min-unique --within e [--maxk K] the call is dg_min_unique_mm (the
+shortest k-mer unique within e mismatches): total and search ms, candidates, probes / steps / table reads / verified rows per candidate
+and the longest launch of the search -- and beside it ONE dg_mappability_mm(k = K, e) pass (the bisection the call replaces needs about
+seven) and the exact dg_min_unique pass, on the same genome and build.  With --query the runs go through dg_query_map (k-mer counts for sequences
 outside the index): one query set of 1 Mb cut from the genome with 1 % substitutions plus 1 Mb random, in records of 10 kb, at e = 0, 1, 2
 per k, positions/s from the call's wall time and from the device time, the search counters per valid position, the longest launch — and,
 at e = 0 in the same run, the route a build without dg_query_map offers to the same numbers: dg_count on every k-mer and its reverse
@@ -38,6 +41,8 @@ ap.add_argument("--ks", default="24,36,50,100,150")
 ap.add_argument("--mismatches", type=int, default=0, help="e of (k,e)-mappability: 0 (exact), 1 or 2")
 ap.add_argument("--min-unique", action="store_true", help="time dg_min_unique (max_k = --maxk) beside one exact pass at k = --maxk")
 ap.add_argument("--maxk", type=int, default=100, help="max_k of --min-unique")
+ap.add_argument("--within", type=int, default=0, help="with --min-unique: e of dg_min_unique_mm (1 or 2), timed beside one dg_mappability_mm(k = --maxk, e) "
+                "pass and the exact dg_min_unique")
 ap.add_argument("--query", action="store_true", help="time dg_query_map on a 2 Mb query set (per k of --ks, e = 0, 1, 2) beside dg_count on its k-mers")
 ap.add_argument("--query-mb", type=float, default=1.0, help="Mb of each half of the --query set (cut from the genome / random)")
 ap.add_argument("--anchor", default="", help="with --query: time dg_query_map_anchored at these anchors (comma-separated; k = the k-mer length) beside "
@@ -59,6 +64,10 @@ ap.add_argument("--workdir", default="/dev/shm")
 a = ap.parse_args()
 if a.min_unique and (a.mismatches or a.maxcount):
     ap.error("--min-unique goes with neither --mismatches nor --maxcount")
+if a.within and not a.min_unique:
+    ap.error("--within goes with --min-unique")
+if a.within not in (0, 1, 2):
+    ap.error("--within is 0, 1 or 2")
 if a.iupac and not a.query:
     ap.error("--iupac goes with --query")
 if a.by_end and not a.query_minlen:
@@ -127,6 +136,44 @@ def min_unique_run(fo):
             "exact_pass_k": a.maxk, "exact_pass_ms_total": round(xs.ms_total, 1), "exact_pass_rev_steps": xs.rev_steps,
             "exact_pass_transient_gb": round(xs.transient_bytes / 1e9, 2),
             "cost_in_exact_passes": round(st.ms_total / max(xs.ms_total, 1e-9), 2)}
+
+
+def min_unique_mm_run(fo):
+    """one dg_min_unique_mm pass at max_k = --maxk, e = --within and, beside it, one dg_mappability_mm pass at k = --maxk with the same e and
+    the exact dg_min_unique pass"""
+    m, x, u = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    prm = _capi.MinUniqueMmParams(a.maxk, a.within, 1 if fo else 0, 0, 0)
+    os.environ["DICEY_TIMING"] = "1"
+    t0 = time.time()
+    err = stderr_of(lambda: _capi.check(L, L.dg_min_unique_mm(ix.handle, C.byref(prm), C.byref(m))))
+    wall = time.time() - t0
+    del os.environ["DICEY_TIMING"]
+    st, mu = _capi.MapStats(), _capi.MuMmStats()
+    _capi.check(L, L.dg_map_stats(m, C.byref(st)))
+    _capi.check(L, L.dg_map_mu_mm_stats(m, C.byref(mu)))
+    L.dg_map_free(m)
+    line = re.search(r"min unique max_k=\d+ e=\d+: (\d+) launches of the search, [0-9.]+ ms in all, longest ([0-9.]+) ms", err)
+    xp = _capi.MapMmParams(a.maxk, a.within, 1 if fo else 0, 0, 0, 0)
+    _capi.check(L, L.dg_mappability_mm(ix.handle, C.byref(xp), C.byref(x)))
+    xs = _capi.MapStats()
+    _capi.check(L, L.dg_map_stats(x, C.byref(xs)))
+    L.dg_map_free(x)
+    up = _capi.MinUniqueParams(a.maxk, 1 if fo else 0, 0, 0)
+    _capi.check(L, L.dg_min_unique(ix.handle, C.byref(up), C.byref(u)))
+    us = _capi.MapStats()
+    _capi.check(L, L.dg_map_stats(u, C.byref(us)))
+    L.dg_map_free(u)
+    c = max(mu.candidates, 1)
+    return {"min_unique": True, "within": a.within, "max_k": a.maxk, "forward_only": fo, "ms_total": round(st.ms_total, 1),
+            "ms_forward": round(st.ms_forward, 1), "ms_reverse": round(st.ms_reverse, 1), "ms_search": round(mu.ms_search, 1),
+            "candidates": mu.candidates, "candidate_share": round(mu.candidates / max(n - 1, 1), 3), "probes_per_candidate": round(mu.probes / c, 2),
+            "steps_per_candidate": round(mu.steps / c, 2), "table_reads_per_candidate": round(mu.table_reads / c, 2),
+            "verified_rows_per_candidate": round(mu.verified_rows / c, 2), "launches": mu.launches,
+            "longest_launch_ms": float(line.group(2)) if line else None, "wall_s": round(wall, 2), "transient_gb": round(st.transient_bytes / 1e9, 2),
+            "mm_pass_k": a.maxk, "mm_pass_ms_total": round(xs.ms_total, 1), "mm_pass_transient_gb": round(xs.transient_bytes / 1e9, 2),
+            "exact_min_unique_ms_total": round(us.ms_total, 1),
+            "cost_in_mm_passes": round(st.ms_total / max(xs.ms_total, 1e-9), 2),
+            "cost_over_seven_passes": round(st.ms_total / max(7 * xs.ms_total, 1e-9), 3)}
 
 
 def query_set():
@@ -441,7 +488,7 @@ elif a.query:
     ks = []
 elif a.min_unique:
     for fo in STRANDS:
-        runs.append(min_unique_run(fo))
+        runs.append(min_unique_mm_run(fo) if a.within else min_unique_run(fo))
         print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
     ks = []
 else:
