@@ -19,6 +19,14 @@
 //                 of dg_query_map) DICEY_QMINLEN_CHUNK (positions per launch of dg_query_min_len) DICEY_MU_MM_RANK_ORDER (dg_min_unique_mm: lanes by rank
 //                 instead of by text position) -- results do not depend on them
 //   search.hip / thal_api.hip   DICEY_NO_LDS_TABLES DICEY_NO_WAVE_THAL DICEY_DEBUG_THAL_REDO DICEY_DEBUG_DUMP_RAW
+//
+// A development build also exports ONE function the header does not declare (index.hip, next to its struct dgx_layout_info):
+//   int dgx_index_layout(dg_index*, uint32_t what, uint32_t level, void* host_out, uint64_t cap_bytes, dgx_layout_info* info)
+// synchronises the handle's stream, copies at most cap_bytes of one derived layout to the host — what: 0 occ, 1 text, 2 sa, 3 ktab,
+// 4 / 5 copy `level` of kf / kf2, 6 pre5, 7 sax, 8 / 9 directory / records of prefix level `level`, 10 block minima of level `level` >= 1
+// — and fills info: the layout's bytes without allocation slack (0 = the handle does not have it: not an error), and FmView's scalars
+// (n, C4, K, nrun_min, nlev, nplv, the level's x, each filter's k / nr / s / pick, whether pre5 / sax are null).  host_out == NULL: info
+// only.  tests/test_gpu_index_layout.py holds every entry of every layout against tests/index_layout_ref.py through it.
 #pragma once
 #include <cstdlib>
 

@@ -248,20 +248,6 @@ DG_DEV void kmer_codes_at(const FmView& f, u64 p, u32 K, u32 K2, u64& code, u64&
   code = got >= K ? acc >> (2 * (24 - K)) : none;
   code2 = (K2 && got >= K2) ? acc >> (2 * (24 - K2)) : none;
 }
-// kf2: copy 0 of the long presence filter (bit address = K2-mer code), zeroed by the caller; nullptr = none
-__global__ void k_kmer_table(FmView f, uint2* tab, u32 K, u32 K2, u32* kf2) {
-  u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= f.n) return;
-  u64 me, me2, prev, next, x2;
-  kmer_codes_at(f, f.sa[i], K, kf2 ? K2 : 0u, me, me2);
-  if (me >> 63) return;
-  prev = next = 1ULL << 63;
-  if (i) kmer_codes_at(f, f.sa[i - 1], K, 0u, prev, x2);
-  if (i + 1 < f.n) kmer_codes_at(f, f.sa[i + 1], K, 0u, next, x2);
-  if (prev != me) tab[me].x = (u32)i;
-  if (next != me) tab[me].y = (u32)(i + 1);
-  if (kf2 && !(me2 >> 63)) atomicOr(&kf2[me2 >> 5], 1u << (me2 & 31));
-}
 
 // ---- presence filter (FmView::kf) ----
 // copy 0 (in-line bits = the low 9 code bits = address order of the table): one coalesced pass over the table
@@ -334,11 +320,6 @@ __global__ void k_kf_generic0(const u32* r0, u32 bits, u32 s, u32* out, u64 nwor
   out[w] = v;
 }
 
-__global__ void k_kf_compare(const u32* a, const u32* b, u64 n, u32* bad) {
-  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n && a[i] != b[i]) atomicAdd(bad, 1u);
-}
-
 // Number of copies, their in-line bit fields (spread evenly over the code) and, per window position, the copy to ask.
 static void kf_layout(KFilter& kf, u32 k) {
   const u32 bits = 2 * k;
@@ -398,8 +379,9 @@ static int build_filter(dg_index* ix, KFilter& kf, u32 k, const uint2* tab, u32*
   return DG_OK;
 }
 
-// The same table with one text gather per lane instead of three: the K-mers of the neighbouring suffixes come from the
-// neighbouring lanes (the first / last lane of a wavefront read theirs).
+// The table fill, one text gather per lane: the K-mers of the neighbouring suffixes come from the neighbouring lanes (the first /
+// last lane of a wavefront read theirs).  kf2: copy 0 of the long presence filter (bit address = K2-mer code), zeroed by the caller;
+// nullptr = none
 __global__ void __launch_bounds__(256) k_kmer_table_wave(FmView f, uint2* tab, u32 K, u32 K2, u32* kf2) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   const u64 none = 1ULL << 63;
@@ -1040,5 +1022,98 @@ int dg_index_stats(const dg_index* ix, dg_index_stats_t* out) {
   out->derive_seconds = ix->derive_seconds;
   return DG_OK;
 }
+
+#ifdef DG_EXPERIMENTS
+// Development builds only (experiments.hpp; not in include/dicey_gpu.h, not exported by the product): the derived layouts as they lie
+// in HBM, for tests/test_gpu_index_layout.py, which holds every entry against tests/index_layout_ref.py.
+enum dgx_layout : uint32_t {
+  DGX_L_OCC = 0,   // OccBlock[plan::occ_blocks(n)]
+  DGX_L_TEXT,      // u8[n]
+  DGX_L_SA,        // u32[n]
+  DGX_L_KTAB,      // uint2[4^K], packed (FmView::ktab)
+  DGX_L_KF,        // copy `level` of kf: u32[4^k / 32]
+  DGX_L_KF2,       // copy `level` of kf2
+  DGX_L_PRE5,      // u16[n]
+  DGX_L_SAX,       // uint2[n]
+  DGX_L_PLV_DIR,   // prefix level `level`: u64[8 * plan::plv_lines(n)]
+  DGX_L_PLV_REC,   // prefix level `level`: uint2[x]
+  DGX_L_SAMIN      // block minima, level `level` >= 1: u32[((nout + 7) & ~7) + 8] — the 0xFFFFFFFF padding belongs to the layout
+};
+struct dgx_filter_info {
+  uint32_t k, nr, s[4];
+  uint64_t pick;
+};
+struct dgx_layout_info {
+  uint64_t bytes;  // of the layout asked for, without the allocation's slack; 0 = this handle does not have it
+  uint64_t n;
+  uint64_t x;      // DGX_L_PLV_*: the level's X, else 0
+  uint32_t C4[4];
+  uint32_t K, nrun_min, nlev, nplv;
+  uint32_t pre5_null, sax_null;
+  dgx_filter_info kf, kf2;
+};
+int dgx_index_layout(dg_index* ix, uint32_t what, uint32_t level, void* host_out, uint64_t cap_bytes, dgx_layout_info* info) {
+  if (!ix || !info) return fail(DG_EINVAL, "dgx_index_layout: null argument");
+  const FmView& f = ix->view;
+  std::memset(info, 0, sizeof *info);
+  info->n = f.n;
+  std::memcpy(info->C4, f.C4, sizeof info->C4);
+  info->K = f.K;
+  info->nrun_min = f.nrun_min;
+  info->nlev = f.nlev;
+  info->nplv = f.nplv;
+  info->pre5_null = f.pre5 == nullptr;
+  info->sax_null = f.sax == nullptr;
+  const KFilter* kfs[2] = {&f.kf, &f.kf2};
+  dgx_filter_info* out[2] = {&info->kf, &info->kf2};
+  for (int i = 0; i < 2; ++i) {
+    out[i]->k = kfs[i]->k;
+    out[i]->nr = kfs[i]->nr;
+    std::memcpy(out[i]->s, kfs[i]->s, sizeof out[i]->s);
+    out[i]->pick = kfs[i]->pick;
+  }
+  const void* src = nullptr;
+  u64 bytes = 0;
+  switch (what) {
+    case DGX_L_OCC: src = f.occ, bytes = plan::occ_blocks(f.n) * sizeof(OccBlock); break;
+    case DGX_L_TEXT: src = f.text, bytes = f.n; break;
+    case DGX_L_SA: src = f.sa, bytes = f.n * 4; break;
+    case DGX_L_KTAB: src = f.K ? f.ktab : nullptr, bytes = f.K ? plan::table_bytes(f.K) : 0; break;
+    case DGX_L_KF:
+    case DGX_L_KF2: {
+      const KFilter& kf = what == DGX_L_KF ? f.kf : f.kf2;
+      if (level < kf.nr) src = kf.cp[level], bytes = plan::filter_bits_bytes(kf.k);
+      break;
+    }
+    case DGX_L_PRE5: src = f.pre5, bytes = f.n * 2; break;
+    case DGX_L_SAX: src = f.sax, bytes = f.n * 8; break;
+    case DGX_L_PLV_DIR:
+    case DGX_L_PLV_REC:
+      if (level < f.nplv) {
+        info->x = f.plv[level].x;
+        if (what == DGX_L_PLV_DIR) src = f.plv[level].dir, bytes = plan::plv_lines(f.n) * 64;
+        else src = f.plv[level].rec, bytes = f.plv[level].x * 8;
+      }
+      break;
+    case DGX_L_SAMIN:
+      if (level >= 1 && level < f.nlev) {
+        u64 cnt = f.n, npad = 0;
+        for (u32 l = 1; l <= level; ++l) {  // stage_block_minima's sizes
+          cnt = (cnt + 7) / 8;
+          npad = ((cnt + 7) & ~7ULL) + 8;
+        }
+        src = f.samin[level], bytes = npad * 4;
+      }
+      break;
+    default: return fail(DG_EINVAL, "dgx_index_layout: unknown layout %u", what);
+  }
+  if (!src) bytes = 0;
+  info->bytes = bytes;
+  DG_HIP(hipSetDevice(ix->device));
+  DG_HIP(hipStreamSynchronize(ix->stream));
+  if (host_out && bytes) DG_HIP(hipMemcpy(host_out, src, (size_t)std::min<u64>(bytes, cap_bytes), hipMemcpyDeviceToHost));
+  return DG_OK;
+}
+#endif
 
 }  // extern "C"
