@@ -1,9 +1,12 @@
-// Helpers shared by the subcommands of the `dicey` host binary (dicey_main.cpp: hunt, search, index; padlock.cpp).
+// Helpers shared by the subcommands of the `dicey` host binary (dicey_main.cpp: search, index; hunt.cpp; padlock.cpp; mappability.cpp).
 #pragma once
 #include <zlib.h>
 
+#include <cctype>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -16,6 +19,19 @@ namespace {
 [[maybe_unused]] const char* kVersion = "0.5.1";  // src/version.h:8 — goes into meta.version
 
 // ------------------------------------------------------------------------------------------------ small utilities
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+inline bool quick_exit_on() {  // DICEY_NO_QUICK_EXIT: close the index and let the HIP runtime unwind (leak checkers, debugging)
+  static const bool on = std::getenv("DICEY_NO_QUICK_EXIT") == nullptr;
+  return on;
+}
+inline bool timing_on() {
+  static const bool on = std::getenv("DICEY_TIMING") != nullptr;
+  return on;
+}
+inline int device_from_env() {
+  const char* e = std::getenv("DICEY_DEVICE");
+  return e ? std::atoi(e) : 0;
+}
 inline bool file_nonempty(const std::string& p) {
   struct stat st;
   return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0;
@@ -144,27 +160,59 @@ inline void uint_append(std::string& o, uint64_t v) {  // std::to_string without
   while (n) o.push_back(buf[--n]);
 }
 
-// one gzip member per call, appended (hunter.h:162-170: gzip_compressor + file_sink(app))
+// The records of a FASTA file as faidx serves them: name = header up to the first whitespace, residues without blanks; `upper`
+// upper-cases them (as `dicey index` does to the genome)
+inline bool read_fasta(const std::string& path, bool upper, std::vector<std::string>& names, std::vector<std::string>& seqs) {
+  LineReader r(path);
+  if (!r.ok()) return false;
+  std::string line;
+  while (r.next(line)) {
+    if (!line.empty() && line[0] == '>') {
+      const size_t e = line.find_first_of(" \t\r", 1);
+      names.push_back(line.substr(1, e == std::string::npos ? std::string::npos : e - 1));
+      seqs.emplace_back();
+    } else if (!seqs.empty()) {
+      if (!upper && line.find_first_of("\r \t") == std::string::npos) seqs.back() += line;  // the usual case: residues only
+      else
+        for (char ch : line)
+          if (!(ch == '\r' || ch == ' ' || ch == '\t')) seqs.back().push_back(upper ? (char)std::toupper((unsigned char)ch) : ch);
+    }
+  }
+  return !seqs.empty();
+}
+
+// one gzip member of `data` at the given deflate level: members written in a row are one file to gzip -dc
+inline bool gzip_member_at(int level, const std::string& data, std::string& out) {
+  z_stream zs;
+  std::memset(&zs, 0, sizeof zs);
+  if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
+  static const unsigned char hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
+  out.assign((const char*)hdr, 10);
+  const size_t bound = deflateBound(&zs, data.size());
+  out.resize(10 + bound + 8);
+  zs.next_in = (Bytef*)data.data();
+  zs.avail_in = (uInt)data.size();
+  zs.next_out = (Bytef*)&out[10];
+  zs.avail_out = (uInt)bound;
+  const int rc = deflate(&zs, Z_FINISH);
+  const size_t used = zs.total_out;
+  deflateEnd(&zs);
+  if (rc != Z_STREAM_END) return false;
+  const uint32_t crc = (uint32_t)crc32(0L, (const Bytef*)data.data(), (uInt)data.size()), isz = (uint32_t)data.size();
+  std::memcpy(&out[10 + used], &crc, 4);
+  std::memcpy(&out[10 + used + 4], &isz, 4);
+  out.resize(10 + used + 8);
+  return true;
+}
+// to a string at level 1: the chunks of a mappability track are members of their own
+inline bool gzip_member(const std::string& data, std::string& out) { return gzip_member_at(1, data, out); }
+// one member per call at the default level, appended to the file (hunter.h:162-170: gzip_compressor + file_sink(app))
 inline bool append_gzip_member(const std::string& path, const std::string& data) {
   FILE* f = std::fopen(path.c_str(), "ab");
   if (!f) return false;
-  static const unsigned char hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
-  std::fwrite(hdr, 1, 10, f);
-  z_stream zs;
-  std::memset(&zs, 0, sizeof zs);
-  deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY);
-  std::vector<unsigned char> out(deflateBound(&zs, data.size()) + 64);
-  zs.next_in = (Bytef*)data.data();
-  zs.avail_in = (uInt)data.size();
-  zs.next_out = out.data();
-  zs.avail_out = (uInt)out.size();
-  deflate(&zs, Z_FINISH);
-  std::fwrite(out.data(), 1, zs.total_out, f);
-  deflateEnd(&zs);
-  uint32_t crc = (uint32_t)crc32(0L, (const Bytef*)data.data(), (uInt)data.size()), isz = (uint32_t)data.size();
-  std::fwrite(&crc, 4, 1, f);
-  std::fwrite(&isz, 4, 1, f);
-  return std::fclose(f) == 0;
+  std::string packed;
+  const bool good = gzip_member_at(Z_DEFAULT_COMPRESSION, data, packed) && std::fwrite(packed.data(), 1, packed.size(), f) == packed.size();
+  return (std::fclose(f) == 0) && good;
 }
 
 // ------------------------------------------------------------------------------------------------ options (boost::program_options subset)
@@ -249,6 +297,5 @@ inline Parsed parse_options(int argc, char** argv, const OptSpec* specs, size_t 
   }
   return p;
 }
-
 
 }  // namespace

@@ -98,30 +98,6 @@ int bail(const std::string& m) {
   return 1;
 }
 
-// one gzip member of `data` (deflate level 1): the chunks of a file are members of their own, which gzip -dc reads in a row
-bool gzip_member(const std::string& data, std::string& out) {
-  z_stream zs;
-  std::memset(&zs, 0, sizeof zs);
-  if (deflateInit2(&zs, 1, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) return false;
-  static const unsigned char hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
-  out.assign((const char*)hdr, 10);
-  const size_t bound = deflateBound(&zs, data.size());
-  out.resize(10 + bound + 8);
-  zs.next_in = (Bytef*)data.data();
-  zs.avail_in = (uInt)data.size();
-  zs.next_out = (Bytef*)&out[10];
-  zs.avail_out = (uInt)bound;
-  const int rc = deflate(&zs, Z_FINISH);
-  const size_t used = zs.total_out;
-  deflateEnd(&zs);
-  if (rc != Z_STREAM_END) return false;
-  const uint32_t crc = (uint32_t)crc32(0L, (const Bytef*)data.data(), (uInt)data.size()), isz = (uint32_t)data.size();
-  std::memcpy(&out[10 + used], &crc, 4);
-  std::memcpy(&out[10 + used + 4], &isz, 4);
-  out.resize(10 + used + 8);
-  return true;
-}
-
 struct Piece {  // the runs of positions [a, b) of one sequence
   uint32_t seq = 0;
   uint64_t a = 0, b = 0;
@@ -129,31 +105,13 @@ struct Piece {  // the runs of positions [a, b) of one sequence
   std::vector<uint32_t> len, value;
 };
 
-// the records of a FASTA file: the header's first word and the sequence, upper-cased (as `dicey index` does to the genome)
-bool read_fasta(const std::string& path, std::vector<std::string>& names, std::vector<std::string>& seqs) {
-  LineReader r(path);
-  if (!r.ok()) return false;
-  std::string line;
-  while (r.next(line)) {
-    if (!line.empty() && line[0] == '>') {
-      const size_t e = line.find_first_of(" \t\r", 1);
-      names.push_back(line.substr(1, e == std::string::npos ? std::string::npos : e - 1));
-      seqs.emplace_back();
-    } else if (!seqs.empty()) {
-      for (char c : line)
-        if (!(c == '\r' || c == ' ' || c == '\t')) seqs.back().push_back((char)std::toupper((unsigned char)c));
-    }
-  }
-  return !seqs.empty();
-}
-
 // bedGraph of the query records: one line per maximal run of equal values over valid positions, zero included.  With lp (-l) the values
 // are minimum lengths and zero, no length, has no line either, and with ep (-l -E) those by end position, at the coordinates of the
 // k-mer's last base; with ap (-a) they are the anchored counts, with ip (-I) those of records with IUPAC codes
 int write_query_map(dg_index* ix, const dg_qmap_params& qp, const dg_qminlen_params* lp, const dg_qminlen_end_params* ep,
                     const dg_qmap_anchor_params* ap, const dg_qmap_iupac_params* ip, const std::string& query, const std::string& outfile) {
   std::vector<std::string> names, seqs;
-  if (!read_fasta(query, names, seqs)) return bail("Error: Could not read any sequence from " + query + "!");
+  if (!read_fasta(query, true, names, seqs)) return bail("Error: Could not read any sequence from " + query + "!");
   std::vector<uint64_t> off(seqs.size() + 1, 0);
   for (size_t i = 0; i < seqs.size(); ++i) off[i + 1] = off[i] + seqs[i].size();
   std::string all;

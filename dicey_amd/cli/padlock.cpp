@@ -103,26 +103,6 @@ double gccontent(const char* s, size_t n) {  // util.h:99-107
   return (double)gc / (double)n;
 }
 
-// Sequences of a FASTA file as faidx serves them: name = header up to the first whitespace, residues as stored
-bool read_fasta(const std::string& path, std::vector<std::string>& names, std::vector<std::string>& seqs) {
-  LineReader r(path);
-  if (!r.ok()) return false;
-  std::string line;
-  while (r.next(line)) {
-    if (!line.empty() && line[0] == '>') {
-      size_t e = line.find_first_of(" \t\r", 1);
-      names.push_back(line.substr(1, e == std::string::npos ? std::string::npos : e - 1));
-      seqs.emplace_back();
-    } else if (!seqs.empty()) {
-      if (line.find_first_of("\r \t") == std::string::npos) seqs.back() += line;  // the usual case: residues only
-      else
-        for (char ch : line)
-          if (!(ch == '\r' || ch == ' ' || ch == '\t')) seqs.back().push_back(ch);
-    }
-  }
-  return !names.empty();
-}
-
 // gtf.h:88-227.  A malformed line stops the parse with a message; the caller carries on with what was read (parseGTF
 // ignores the return value of parseGTFAll).
 void parse_gtf_all(const PadlockConfig& c, std::vector<std::vector<IntervalLabel>>& regs, std::vector<GeneInfo>& geneInfo) {
@@ -404,7 +384,7 @@ int run_padlock(PadlockConfig& c) {  // padlock.h:147-531
   }
   // sequences the exons are cut from: the genome, or the input FASTA (padlock.h:310-312)
   std::vector<std::string> srcname, srcseq;
-  if (!read_fasta(c.inputFasta ? c.infile : c.genome, srcname, srcseq)) {
+  if (!read_fasta(c.inputFasta ? c.infile : c.genome, false, srcname, srcseq)) {
     std::cerr << "Error: Cannot read " << (c.inputFasta ? c.infile : c.genome) << std::endl;
     return 1;
   }
