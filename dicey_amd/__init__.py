@@ -237,6 +237,73 @@ class FmIndex:
         finally:
             self._L.dg_map_free(m)
 
+    def _cover(self, k, at_most, forward_only, max_count, mismatches):
+        """the count map at k with max_count = at_most + 1 (only `<= at_most` is asked of it, so a search with mismatches may stop
+        early), transformed; the count map is freed"""
+        base = self._map(k, forward_only, min(at_most, 0xFFFFFFFD) + 1, mismatches)
+        try:
+            m = C.c_void_p()
+            prm = _capi.CoverParams(at_most, max_count, 0, 0)
+            _capi.check(self._L, self._L.dg_map_cover(self._h, base, C.byref(prm), C.byref(m)))
+            return m
+        finally:
+            self._L.dg_map_free(base)
+
+    def _min_cover(self, max_k, forward_only, mismatches):
+        base = self._min_unique(max_k, forward_only, mismatches)
+        try:
+            m = C.c_void_p()
+            prm = _capi.MinCoverParams(0, 0)
+            _capi.check(self._L, self._L.dg_map_min_cover(self._h, base, C.byref(prm), C.byref(m)))
+            return m
+        finally:
+            self._L.dg_map_free(base)
+
+    def _cover_array(self, m, stats):
+        cs = _capi.CoverStats()
+        self._L.dg_map_cover_stats(m, C.byref(cs))  # (refuses null pointers only)
+        out = self._map_array(m, stats)  # (frees the map)
+        if stats is not None:  # behind dg_map_stats_t, whose transient_bytes is 0 for a transform
+            stats.update({f: getattr(cs, f) for f, _ in _capi.CoverStats._fields_})
+        return out
+
+    def _runs_of(self, m, lo, hi):
+        """the runs of a dg_map inside [lo, hi) (hi = n-1 when None); frees the map"""
+        try:
+            if hi is None:
+                st = _capi.MapStats()
+                _capi.check(self._L, self._L.dg_map_stats(m, C.byref(st)))
+                hi = st.n - 1
+            return self._map_runs(m, lo, hi)
+        finally:
+            self._L.dg_map_free(m)
+
+    def cover(self, k: int = 100, at_most: int = 1, forward_only: bool = False, max_count: int = 0, mismatches: int = 0,
+              stats: Optional[dict] = None):
+        """Per-base cover count (include/dicey_gpu.h dg_map_cover): numpy uint32 array of n-1 values, value[p] = the number of k-mers that
+        lie over base p, starts max(0, p-k+1) .. p, whose mappability(k, mismatches=mismatches) is in 1..at_most (at_most = 1: unique
+        k-mers); min(value, max_count) when max_count > 0, so max_count = 1 is the single-read mappability track and value / k the
+        multi-read one.  `stats`, when given, receives dg_cover_stats_t (specific, covered, ms_bits, ms_cover) and the transform's
+        dg_map_stats_t (ms_total)."""
+        return self._cover_array(self._cover(k, at_most, forward_only, max_count, mismatches), stats)
+
+    def cover_runs(self, k: int = 100, at_most: int = 1, forward_only: bool = False, max_count: int = 0, mismatches: int = 0,
+                   lo: int = 0, hi: Optional[int] = None):
+        """The same counts as maximal runs of equal non-zero values inside text positions [lo, hi) (hi = n-1 when None): numpy
+        arrays (start uint64, length uint32, value uint32); a run is cut at lo and hi."""
+        return self._runs_of(self._cover(k, at_most, forward_only, max_count, mismatches), lo, hi)
+
+    def min_cover(self, max_k: int = 100, forward_only: bool = False, mismatches: int = 0, stats: Optional[dict] = None):
+        """Minimum covering length of every base (include/dicey_gpu.h dg_map_min_cover): numpy uint32 array of n-1 values, value[p] = the
+        length of the shortest unique window of A/C/G/T, at most max_k, that contains base p (unique within `mismatches` substitutions,
+        as min_unique), 0 where there is none: the minimum read length at which the base is uniquely mappable.  `stats`, when given,
+        receives dg_cover_stats_t and the transform's dg_map_stats_t."""
+        return self._cover_array(self._min_cover(max_k, forward_only, mismatches), stats)
+
+    def min_cover_runs(self, max_k: int = 100, forward_only: bool = False, mismatches: int = 0, lo: int = 0, hi: Optional[int] = None):
+        """The same lengths as maximal runs of equal non-zero values inside text positions [lo, hi) (hi = n-1 when None)."""
+        return self._runs_of(self._min_cover(max_k, forward_only, mismatches), lo, hi)
+
     def _query(self, fn, prm, st, seqs, stats):
         """One dg_query_* call: upper-case and pack the records, call `fn` with the parameter block `prm`, copy the stats struct `st`
         into `stats` and split the values per record."""

@@ -160,6 +160,22 @@ class MuMmStats(C.Structure):
                 ("verified_rows", C.c_uint64), ("launches", C.c_uint64), ("ms_search", C.c_double)]
 
 
+class CoverParams(C.Structure):
+    _fields_ = [("at_most", C.c_uint32), ("max_count", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MinCoverParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CoverStats(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("k", C.c_uint32), ("at_most", C.c_uint32), ("max_count", C.c_uint32), ("specific", C.c_uint64),
+                ("covered", C.c_uint64), ("ms_bits", C.c_double), ("ms_cover", C.c_double), ("transient_bytes", C.c_uint64)]
+
+
+DG_MAP_KIND_COUNT, DG_MAP_KIND_LENGTH, DG_MAP_KIND_COVER, DG_MAP_KIND_MIN_COVER = 0, 1, 2, 3
+
+
 # every symbol include/dicey_gpu.h declares; tests/test_capi_symbols.py checks the list against the header
 class PadlockParams(C.Structure):
     _fields_ = [("armlen", C.c_uint32), ("distance", C.c_uint32), ("hamming", C.c_int32), ("tmdiff", C.c_uint32),
@@ -182,7 +198,8 @@ SYMBOLS = ["dg_index_open", "dg_index_close", "dg_index_stats", "dg_count", "dg_
            "dg_chit_unpack", "dg_normalize_query", "dg_hunt_expand", "dg_index_stream", "dg_fm9_check",
            "dg_mappability", "dg_map_values", "dg_map_runs", "dg_map_device_values", "dg_map_stats", "dg_map_free",
            "dg_mappability_mm", "dg_map_mm_stats", "dg_min_unique", "dg_query_map", "dg_query_min_len",
-           "dg_query_map_anchored", "dg_query_min_len_end", "dg_query_map_iupac", "dg_min_unique_mm", "dg_map_mu_mm_stats"]
+           "dg_query_map_anchored", "dg_query_min_len_end", "dg_query_map_iupac", "dg_min_unique_mm", "dg_map_mu_mm_stats",
+           "dg_map_cover", "dg_map_min_cover", "dg_map_cover_stats"]
 
 _lib = None
 
@@ -266,6 +283,9 @@ def load(path=None):
     L.dg_query_map_anchored.argtypes = [vp, C.POINTER(QmapAnchorParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapStats)]
     L.dg_query_min_len_end.argtypes = [vp, C.POINTER(QminlenEndParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QminlenStats)]
     L.dg_query_map_iupac.argtypes = [vp, C.POINTER(QmapIupacParams), C.c_char_p, u64p, C.c_size_t, u32p, C.POINTER(QmapIupacStats)]
+    L.dg_map_cover.argtypes = [vp, vp, C.POINTER(CoverParams), C.POINTER(vp)]
+    L.dg_map_min_cover.argtypes = [vp, vp, C.POINTER(MinCoverParams), C.POINTER(vp)]
+    L.dg_map_cover_stats.argtypes = [vp, C.POINTER(CoverStats)]
     L.dg_map_free.restype = None
     if path is None:
         _lib = L

@@ -9,6 +9,8 @@
 // With -q -a the last -a bases of every k-mer, the oligo's 3' end, must match exactly (dg_query_map_anchored).
 // With -q -l -E the length is that of the shortest specific k-mer that ENDS at the position, its last -a bases exact (dg_query_min_len_end).
 // With -q -I the records may hold IUPAC codes, each letter a set of bases (dg_query_map_iupac).
+// With -p the value is per BASE: the number of k-mers over the base with at most -t places (dg_map_cover), or with -u -p the length of the
+// shortest unique window that contains the base (dg_map_min_cover).  Both are device transforms of the map the command makes anyway.
 #include <zlib.h>
 
 #include <algorithm>
@@ -30,10 +32,12 @@ const OptSpec kMapOpts[] = {{"help", '?', false},  {"genome", 'g', true},  {"kme
                             {"query", 'q', true}, {"minlength", 'l', false}, {"shortest", 's', true},
                             {"atmost", 't', true}, {"anchor", 'a', true},
                             {"byend", 'E', false}, {"iupac", 'I', false}, {"maxdegeneracy", 'D', true},
-                            {"within", 'w', true}};
+                            {"within", 'w', true}, {"perbase", 'p', false}};
 
 void map_usage() {
   std::cout << "Usage: dicey mappability [OPTIONS] -g genome.fa.gz [-q targets.fa.gz]" << std::endl;
+  std::cout << "       dicey mappability -g genome.fa.gz -p [-k 100] [-e 0] [-f] [-t 1] [-c 0] [-o out.bedgraph.gz]" << std::endl;
+  std::cout << "       dicey mappability -g genome.fa.gz -u -p [-k 100] [-w 0] [-f] [-o out.bedgraph.gz]" << std::endl;
   std::cout << "Generic options:\n"
                "  -? [ --help ]                      show help message\n"
                "  -g [ --genome ] arg                genome file (indexed with dicey index: <genome stem>.fm9)\n"
@@ -48,6 +52,9 @@ void map_usage() {
                "  -l [ --minlength ]                 with -q: write the shortest specific length instead; -k is then the largest length tried\n"
                "  -s [ --shortest ] arg (=10)        with -l: the smallest length tried (10..1000, at most -k)\n"
                "  -t [ --atmost ] arg (=0)           with -l: a length is specific when its k-mer has at most this many places in the genome\n"
+               "                                     with -p: a k-mer counts when its value is at most arg (=1, 1..4294967293)\n"
+               "  -p [ --perbase ]                   write a value per base instead of per k-mer start: the number of k-mers over the base whose\n"
+               "                                     value is at most -t; -c then clamps that number.  With -u: the shortest unique length over the base\n"
                "  -a [ --anchor ] arg                with -q: the last arg bases of every k-mer must match exactly (0..-k)\n"
                "  -E [ --byend ]                     with -l: the length of the shortest specific k-mer that ENDS at the position; -a then 0..-s\n"
                "  -I [ --iupac ]                     with -q: the records may hold IUPAC codes (R Y S W K M B D H V N), each a set of bases; -k 10..64\n"
@@ -90,6 +97,12 @@ void map_usage() {
                "letters must hold the genome's bases, and every k-mer of the genome counts once however many expansions of the record's k-mer it\n"
                "is close to.  Positions whose k-mer has more than -D expansions have no line; their number is reported on stderr.  -I cannot be\n"
                "combined with -l, -u or -E, and -k is at most 64 then.\n"
+               "With -p the value of a base is the number of the up to -k k-mers that lie over it whose value, as written without -p, is between\n"
+               "1 and -t: with the default -t 1 the unique k-mers over the base.  -c 1 writes the single-read mappability track (the base is\n"
+               "covered by at least one uniquely mappable k-mer), the value divided by -k is the multi-read mappability.  Bases that no such\n"
+               "k-mer covers have no line.  With -u -p the value of a base is the length of the shortest unique window (at most -k, within -w\n"
+               "mismatches) that contains it: the minimum read length at which the base is uniquely mappable, in one track.  -p cannot be\n"
+               "combined with -q, and -t has no meaning with -u.\n"
                "\n";
 }
 
@@ -205,7 +218,7 @@ int mappability_main(int argc, char** argv) {
   }
   std::string genome, outfile, query;
   bool help = false, have_genome = false, forward = false, minunique = false, have_query = false, minlength = false, have_shortest = false,
-       have_atmost = false, have_anchor = false, byend = false, iupac = false, have_maxdeg = false, have_within = false;
+       have_atmost = false, have_anchor = false, byend = false, iupac = false, have_maxdeg = false, have_within = false, perbase = false;
   long long k = 100, maxcount = 0, mismatches = 0, shortest = 10, atmost = 0, anchor = 0, maxdeg = 256, within = 0;
   for (auto& kv : p.kv) {
     if (kv.first == "help") help = true;
@@ -224,6 +237,7 @@ int mappability_main(int argc, char** argv) {
     else if (kv.first == "byend") byend = true;
     else if (kv.first == "iupac") iupac = true;
     else if (kv.first == "maxdegeneracy") { maxdeg = std::strtoll(kv.second.c_str(), nullptr, 10); have_maxdeg = true; }
+    else if (kv.first == "perbase") perbase = true;
     else if (kv.first == "within") { within = std::strtoll(kv.second.c_str(), nullptr, 10); have_within = true; }
   }
   if (help || !have_genome || !p.positional.empty()) {
@@ -237,7 +251,11 @@ int mappability_main(int argc, char** argv) {
   if (minunique && have_query) return bail("Error: --minunique cannot be combined with --query!");
   if (minlength && !have_query) return bail("Error: --minlength needs --query!");
   if (minlength && maxcount != 0) return bail("Error: --minlength cannot be combined with --maxcount!");
-  if ((have_shortest || have_atmost) && !minlength) return bail("Error: --shortest and --atmost need --minlength!");
+  if (perbase && have_query) return bail("Error: --perbase cannot be combined with --query!");
+  if (perbase && minunique && have_atmost) return bail("Error: --perbase --minunique cannot be combined with --atmost!");
+  if (perbase && !have_atmost) atmost = 1;
+  if (perbase && (atmost < 1 || atmost > 0xFFFFFFFDll)) return bail("Error: atmost " + std::to_string(atmost) + " outside 1..4294967293!");
+  if ((have_shortest || (have_atmost && !perbase)) && !minlength) return bail("Error: --shortest and --atmost need --minlength!");
   if (shortest < 10 || shortest > 1000) return bail("Error: shortest length " + std::to_string(shortest) + " outside 10..1000!");
   if (shortest > k) return bail("Error: shortest length " + std::to_string(shortest) + " above the largest length " + std::to_string(k) + " (-k)!");
   if (atmost < 0 || atmost > 0xFFFFFFFDll) return bail("Error: atmost " + std::to_string(atmost) + " outside 0..4294967293!");
@@ -289,12 +307,22 @@ int mappability_main(int argc, char** argv) {
     return write_query_map(ix, qp, minlength && !byend ? &lp : nullptr, byend ? &ep : nullptr, have_anchor && !byend && !iupac ? &ap : nullptr,
                            iupac ? &ip : nullptr, query, outfile);
   }
-  dg_map_mm_params mp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, (uint32_t)maxcount, 0u, 0u};
+  // -p: the count map needs to tell 1..atmost from more, nothing else, so its search may stop at atmost + 1; -c clamps the cover count
+  dg_map_mm_params mp = {(uint32_t)k, (uint32_t)mismatches, forward ? 1 : 0, perbase ? (uint32_t)atmost + 1u : (uint32_t)maxcount, 0u, 0u};
   dg_min_unique_params up = {(uint32_t)k, forward ? 1 : 0, 0u, 0u};
   dg_min_unique_mm_params wp = {(uint32_t)k, (uint32_t)within, forward ? 1 : 0, 0u, 0u};
   dg_map* m = nullptr;
   if ((minunique ? (within ? dg_min_unique_mm(ix, &wp, &m) : dg_min_unique(ix, &up, &m)) : dg_mappability_mm(ix, &mp, &m)) != DG_OK)
     return bail(std::string("dicey: ") + dg_last_error());
+  if (perbase) {  // the per-base transform of the map just made, which is then dropped
+    const dg_cover_params cp = {(uint32_t)atmost, (uint32_t)maxcount, 0u, 0u};
+    const dg_min_cover_params np = {0u, 0u};
+    dg_map* pb = nullptr;
+    const int rc = minunique ? dg_map_min_cover(ix, m, &np, &pb) : dg_map_cover(ix, m, &cp, &pb);
+    dg_map_free(m);
+    m = pb;
+    if (rc != DG_OK) return bail(std::string("dicey: ") + dg_last_error());
+  }
   struct MapFreer {
     dg_map* m;
     ~MapFreer() { dg_map_free(m); }

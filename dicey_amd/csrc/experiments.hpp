@@ -17,7 +17,7 @@
 //   mappability.hip   DICEY_MAP_CHUNK (positions per dg_map_runs pass) DICEY_MAP_HEAD_CHUNK (ranks per launch of the e >= 1 search, of dg_min_unique and of dg_min_unique_mm)
 //                 DICEY_MAP_NARROW (W: intervals of at most W rows are verified on the text; 0 = never) DICEY_QMAP_CHUNK (positions per launch
 //                 of dg_query_map) DICEY_QMINLEN_CHUNK (positions per launch of dg_query_min_len) DICEY_MU_MM_RANK_ORDER (dg_min_unique_mm: lanes by rank
-//                 instead of by text position) -- results do not depend on them
+//                 instead of by text position) DICEY_COVER_TILE (positions per k_min_cover workgroup tile, 1..2048) -- results do not depend on them
 //   search.hip / thal_api.hip   DICEY_NO_LDS_TABLES DICEY_NO_WAVE_THAL DICEY_DEBUG_THAL_REDO DICEY_DEBUG_DUMP_RAW
 //
 // A development build also exports ONE function the header does not declare (index.hip, next to its struct dgx_layout_info):

@@ -21,6 +21,8 @@
 // smallest k at which that count is at most t.  dg_query_map_anchored (query_anchor.hpp) is dg_query_map with the last a bases of every
 // k-mer matched exactly.  dg_query_min_len_end (query_min_len_end.hpp) looks for the smallest k by the oligo's LAST base, anchored.
 // dg_query_map_iupac (query_iupac.hpp) is dg_query_map_anchored for records with IUPAC codes, each letter a set of bases.
+// dg_map_cover and dg_map_min_cover (map_cover.hpp) turn a resident map of values per k-mer START into one of values per BASE: the
+// specific k-mers that lie over each base, and the shortest unique window that contains it.  Streaming passes over the map, no search.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -36,6 +38,7 @@
 #include "devfm.hpp"
 #include "experiments.hpp"
 #include "index_internal.hpp"
+#include "map_cover.hpp"        // per-base tracks of a resident map (dg_map_cover, dg_map_min_cover)
 #include "map_mm.hpp"           // k_heads' sibling for e >= 1 mismatches
 #include "min_unique.hpp"         // the kernels of dg_min_unique
 #include "min_unique_mm.hpp"      // and the search with a mismatch budget on top of them (dg_min_unique_mm)
@@ -54,6 +57,9 @@ struct dg_map {
   dg_map_stats_t st{};
   dg_map_mm_stats_t mm{};  // all zero for an exact map
   dg_mu_mm_stats_t mu{};   // all zero unless dg_min_unique_mm searched with mismatches
+  dg_cover_stats_t cv{};   // all zero unless dg_map_cover or dg_map_min_cover made the map
+  uint32_t kind = DG_MAP_KIND_COUNT;  // what the values are: dg_map_cover and dg_map_min_cover ask
+  uint32_t max_count = 0;             // the clamp the values were written with (0: none)
   dg::DevBuf run_flags, run_pos, run_val, run_cnt;  // dg_map_runs workspaces (grow-only)
   ~dg_map() {
     (void)hipSetDevice(device);
@@ -665,6 +671,82 @@ static int query_call(dg_index* ix, const uint8_t* seqs, const uint64_t* off, si
   return DG_OK;
 }
 
+// default positions per k_min_cover workgroup tile (DICEY_COVER_TILE on the development build: a small genome then spans hundreds of tiles
+// and a long halo several of them; results do not depend on it)
+static constexpr u32 COVER_TILE = 2048;
+
+// What dg_map_cover (min_cover false) and dg_map_min_cover do once their arguments are checked.  Everything runs on src's stream, which
+// orders the transform behind whatever still reads or wrote src; the index contributes only its text, an immutable block.
+static int cover_impl(const char* who, dg_index* ix, const dg_map* src, bool min_cover, u32 at_most, u32 max_count, dg_map* m) {
+  const u64 n = src->n;
+  const u32 k = src->st.k;
+  hipStream_t st = src->stream;
+  const u64 nw = (n + 63) / 64 + 1;
+  size_t scan_bytes = 0;
+  if (!min_cover)
+    DG_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, rocprim::make_transform_iterator((const u64*)nullptr, PopcWord{}), (u32*)nullptr, 0u, (size_t)nw,
+                                   rocprim::plus<u32>(), st));
+  const u64 transient = min_cover ? sizeof(CoverCounters) : nw * 8 + nw * 4 + 512 + scan_bytes + sizeof(CoverCounters);
+  const u64 need = n * 4 + 256 + transient + 64;
+  size_t free_b = 0, total_b = 0;
+  DG_HIP(hipMemGetInfo(&free_b, &total_b));
+  if ((u64)free_b < need + (64ULL << 20))
+    return fail(DG_ENOMEM, "%s: needs %llu MB of device memory, %llu MB free", who, (unsigned long long)(need >> 20), (unsigned long long)(free_b >> 20));
+  StreamScratch b(st);
+  void *b_words = nullptr, *b_dir = nullptr, *b_scan = nullptr, *b_ctr = nullptr;
+  DG_HIP(big_alloc((void**)&m->out, n * 4 + 256, st));
+  if (!min_cover) {
+    DG_TRY(b.big(&b_words, nw * 8 + 256));
+    DG_TRY(b.big(&b_dir, nw * 4 + 256));
+    DG_TRY(b.small(&b_scan, scan_bytes + 256));
+  }
+  DG_TRY(b.small(&b_ctr, sizeof(CoverCounters)));
+  u32 tile = COVER_TILE;
+  if (const char* e = exp_env("DICEY_COVER_TILE")) tile = (u32)std::min<u64>(std::max<u64>(1, std::strtoull(e, nullptr, 10)), COVER_TILE_MAX);
+  ChunkTimer<2> tm;  // the bitmap and its directory | the per-base kernel
+  DG_TRY(tm.init());
+  const u32 TB = 256;
+  CoverCounters* ctr = (CoverCounters*)b_ctr;
+  DG_HIP(hipMemsetAsync(b_ctr, 0, sizeof(CoverCounters), st));
+  DG_HIP(hipEventRecord(tm.ev[0], st));
+  if (min_cover) {
+    DG_HIP(hipEventRecord(tm.ev[1], st));
+    hipLaunchKernelGGL(k_min_cover, dim3(ceil_div(n, tile)), dim3(TB), 0, st, (const u32*)src->out, ix->view.text, n, k, tile, m->out, ctr);
+  } else {
+    u64* words = (u64*)b_words;
+    u32* dir = (u32*)b_dir;
+    hipLaunchKernelGGL(k_spec_bits, dim3(ceil_div(nw, 16)), dim3(TB), 0, st, (const u32*)src->out, n - 1, at_most, words, nw);
+    DG_HIP(rocprim::exclusive_scan(b_scan, scan_bytes, rocprim::make_transform_iterator((const u64*)words, PopcWord{}), dir, 0u, (size_t)nw,
+                                   rocprim::plus<u32>(), st));
+    DG_HIP(hipEventRecord(tm.ev[1], st));
+    hipLaunchKernelGGL(k_cover, dim3(ceil_div(n, COVER_PER_BLOCK)), dim3(TB), 0, st, (const u64*)words, (const u32*)dir, n, k, max_count, m->out, ctr);
+  }
+  DG_HIP(hipEventRecord(tm.ev[2], st));
+  CoverCounters hc{};
+  u32 total_bits = 0;  // the directory entry of the padding word behind the data: every set bit lies in front of it
+  DG_HIP(hipMemcpyAsync(&hc, b_ctr, sizeof hc, hipMemcpyDeviceToHost, st));
+  if (!min_cover) DG_HIP(hipMemcpyAsync(&total_bits, (const u32*)b_dir + (nw - 1), 4, hipMemcpyDeviceToHost, st));
+  DG_HIP(hipStreamSynchronize(st));
+  DG_HIP(hipGetLastError());
+  float ms[2] = {0, 0}, longest = 0;
+  DG_TRY(tm.read(ms, 1, &longest));
+  m->cv.kind = m->kind;
+  m->cv.k = k;
+  m->cv.at_most = at_most;
+  m->cv.max_count = max_count;
+  u64 specific = total_bits, covered = 0;
+  for (u32 j = 0; j < COVER_SLOTS * COVER_SLOT_STRIDE; j += COVER_SLOT_STRIDE) {
+    specific += hc.specific[j];
+    covered += hc.covered[j];
+  }
+  m->cv.specific = specific;
+  m->cv.covered = covered;
+  m->cv.ms_bits = min_cover ? 0.0 : (double)ms[0];
+  m->cv.ms_cover = ms[1];
+  m->cv.transient_bytes = transient;
+  m->st.ms_total = m->cv.ms_bits + m->cv.ms_cover;
+  return DG_OK;
+}
 
 }  // namespace dg
 
@@ -684,6 +766,8 @@ static int map_open(dg_index* ix, const dg_map_params* p, u32 mismatches, int mo
   m->n = ix->view.n;
   m->st.n = ix->view.n;
   m->st.k = p->k;
+  m->kind = mode ? DG_MAP_KIND_LENGTH : DG_MAP_KIND_COUNT;
+  m->max_count = mode ? 0u : p->max_count;
   if (hipStreamCreate(&m->stream) != hipSuccess) {
     delete m;
     return fail(DG_EHIP, "%s: cannot create a stream", who);
@@ -817,6 +901,61 @@ int dg_map_mm_stats(const dg_map* m, dg_map_mm_stats_t* out) {
 int dg_map_mu_mm_stats(const dg_map* m, dg_mu_mm_stats_t* out) {
   if (!m || !out) return fail(DG_EINVAL, "dg_map_mu_mm_stats: null argument");
   *out = m->mu;
+  return DG_OK;
+}
+
+// the checks behind the parameter block that dg_map_cover and dg_map_min_cover share, then the transform
+static int cover_open(const char* who, dg_index* ix, const dg_map* src, bool min_cover, u32 at_most, u32 max_count, dg_map** out) {
+  if (!ix) return fail(DG_EINVAL, "%s: null argument", who);
+  if (min_cover ? src->kind != DG_MAP_KIND_LENGTH : src->kind != DG_MAP_KIND_COUNT)
+    return fail(DG_EINVAL, "%s: the source map holds %s, not %s", who,
+                src->kind == DG_MAP_KIND_COUNT ? "counts" : src->kind == DG_MAP_KIND_LENGTH ? "lengths" : "per-base values", min_cover ? "lengths" : "counts");
+  if (src->n != ix->view.n || src->device != ix->device)
+    return fail(DG_EINVAL, "%s: the source map is of an index of %llu suffixes on device %d, the handle's has %llu on device %d", who,
+                (unsigned long long)src->n, src->device, (unsigned long long)ix->view.n, ix->device);
+  if (!min_cover && src->max_count && at_most >= src->max_count)
+    return fail(DG_EINVAL, "%s: the source map was made with max_count = %u and cannot tell counts up to at_most = %u apart", who, src->max_count, at_most);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(DG_ENODEV, "%s: no HIP device available", who);
+  DG_HIP(hipSetDevice(src->device));
+  dg_map* m = new dg_map;
+  m->device = src->device;
+  m->n = src->n;
+  m->st.n = src->n;
+  m->st.k = src->st.k;
+  m->kind = min_cover ? DG_MAP_KIND_MIN_COVER : DG_MAP_KIND_COVER;
+  m->max_count = max_count;
+  if (hipStreamCreate(&m->stream) != hipSuccess) {
+    delete m;
+    return fail(DG_EHIP, "%s: cannot create a stream", who);
+  }
+  const int rc = cover_impl(who, ix, src, min_cover, at_most, max_count, m);
+  if (rc != DG_OK) {
+    delete m;
+    return rc;
+  }
+  *out = m;
+  return DG_OK;
+}
+
+int dg_map_cover(dg_index* ix, const dg_map* src, const dg_cover_params* p, dg_map** out) {
+  if (out) *out = nullptr;
+  if (!p || !out || !src) return fail(DG_EINVAL, "dg_map_cover: null argument");
+  if (p->flags || p->reserved) return fail(DG_EINVAL, "dg_map_cover: flags and reserved must be 0");
+  if (p->at_most < 1 || p->at_most > 0xFFFFFFFDu) return fail(DG_ELIMIT, "dg_map_cover: at_most = %u outside 1..4294967293", p->at_most);
+  return cover_open("dg_map_cover", ix, src, false, p->at_most, p->max_count, out);
+}
+
+int dg_map_min_cover(dg_index* ix, const dg_map* src, const dg_min_cover_params* p, dg_map** out) {
+  if (out) *out = nullptr;
+  if (!p || !out || !src) return fail(DG_EINVAL, "dg_map_min_cover: null argument");
+  if (p->flags || p->reserved) return fail(DG_EINVAL, "dg_map_min_cover: flags and reserved must be 0");
+  return cover_open("dg_map_min_cover", ix, src, true, 0u, 0u, out);
+}
+
+int dg_map_cover_stats(const dg_map* m, dg_cover_stats_t* out) {
+  if (!m || !out) return fail(DG_EINVAL, "dg_map_cover_stats: null argument");
+  *out = m->cv;
   return DG_OK;
 }
 

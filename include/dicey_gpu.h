@@ -44,7 +44,8 @@ extern "C" {
  * 7 (additive exports, same version): dg_query_map (the same counts for the k-mers of sequences outside the index)
  * 7 (additive exports, same version): dg_min_unique (the shortest unique k-mer at each position)
  * 7 (additive exports, same version): dg_query_min_len (the shortest specific k-mer at each position of sequences outside the index)
- * 7 (additive exports, same version): dg_min_unique_mm, dg_map_mu_mm_stats (the shortest k-mer unique within up to two mismatches) */
+ * 7 (additive exports, same version): dg_min_unique_mm, dg_map_mu_mm_stats (the shortest k-mer unique within up to two mismatches)
+ * 7 (additive exports, same version): dg_map_cover, dg_map_min_cover, dg_map_cover_stats (per-base tracks: the unique k-mers over each base) */
 #define DG_ABI_VERSION 7
 
 enum {
@@ -575,6 +576,73 @@ typedef struct {
   double ms_search;       /* device time of the search, behind the two exact passes */
 } dg_mu_mm_stats_t;
 int dg_map_mu_mm_stats(const dg_map* m, dg_mu_mm_stats_t* out);
+
+/* ABI 7, additive.  Per-base tracks: device transforms of a dg_map that is already resident.  Every call above gives a value per k-mer
+ * START position; these give a value per BASE, the form Umap and ENCODE publish.  T, "valid window", value_k, value_{e,k}, run, mul and
+ * mul_e are those above; positions are p in [0, n-1).
+ *
+ * Cover count (dg_map_cover).  src is a count map made at length k by dg_mappability or dg_mappability_mm, t = at_most >= 1:
+ *   spec(q)    = 1 iff 1 <= src(q) <= t   (t = 1: the k-mer that starts at q is unique),
+ *   cover_t(p) = #{q : max(0, p-k+1) <= q <= p, spec(q) = 1}, the number of specific k-mers that lie over base p, in 0..k;
+ * max_count = C > 0 writes min(cover, C).  C = 1 is the single-read mappability track (is this base covered by at least one uniquely
+ * mappable k-mer?), cover / k the multi-read one.  A k-mer never crosses a sequence, an N or the text's end because src is 0 at those
+ * starts; no boundary rule is needed beyond that.  The work per base does not grow with k (a bitmap of spec, a rank directory over it,
+ * two ranks per base).
+ *
+ * Minimum covering length (dg_map_min_cover).  src is a length map made with max_k by dg_min_unique or dg_min_unique_mm (any mismatches,
+ * any forward_only):
+ *   mcl(p) = min{max(src(q), p-q+1) : p-max_k+1 <= q <= p, q >= 0, src(q) != 0, run(q) >= p-q+1}, and 0 when the set is empty:
+ * the length of the shortest unique valid window, at most max_k, that contains base p, i.e. the minimum read length at which the base is
+ * uniquely mappable.  (A window that starts at q with length m >= mul(q) inside q's run is unique, because value never rises with the
+ * length.)
+ *
+ * The identity that ties the two together: for every k in 10..max_k and every p that lies in at least one VALID k-window,
+ *   cover_1 at k is >= 1 at p   <=>   mcl(p) != 0 && mcl(p) <= k.
+ * =>: a unique valid k-window at q over p has 0 != mul(q) <= k, run(q) >= k and p-q+1 <= k.  <=: mcl(p) = m <= k names a unique valid
+ * window U of m bases over p; p lies in a valid k-window, so the A/C/G/T run around p holds at least k bases and U can be grown inside it
+ * to a valid k-window W over p; W is unique, on both strands and with mismatches, because every place within e of W holds a place within
+ * e of U at the matching offset, and U has one.  The restriction is needed: a base in an A/C/G/T run shorter than k can have
+ * mcl(p) <= k while no k-window covers it.
+ *
+ * Both calls run on src's own stream and read only src and immutable blocks of the index, so a dg_hunt_submit batch in flight on the
+ * handle does not refuse them.  src is left untouched and stays usable; it may be freed before the result.  The result is an ordinary
+ * dg_map with a stream of its own, synchronised before return: dg_map_values / dg_map_runs / dg_map_device_values / dg_map_free serve
+ * it; its dg_map_stats has n, k (src's k or max_k) and ms_total (the transform), everything else 0.  A call needs 4n bytes for the
+ * result, plus n/8 + n/16 and the scan's scratch for the cover transform; the min-cover transform holds nothing beside its counters.
+ * Checked in this order, *out cleared on every failure: a null parameter block, out or src DG_EINVAL; non-zero flags or reserved
+ * DG_EINVAL; at_most outside 1..0xFFFFFFFD DG_ELIMIT; a null handle DG_EINVAL; src of the wrong kind (a length or per-base map given to
+ * dg_map_cover, anything but a length map given to dg_map_min_cover) DG_EINVAL; src from an index with another n or device DG_EINVAL; src
+ * made with max_count = C > 0 and at_most >= C, whose clamped values cannot answer the test, DG_EINVAL; no device DG_ENODEV; free HBM,
+ * before any kernel and with every buffer allocated first, DG_ENOMEM. */
+#define DG_MAP_KIND_COUNT 0u     /* dg_mappability, dg_mappability_mm */
+#define DG_MAP_KIND_LENGTH 1u    /* dg_min_unique, dg_min_unique_mm */
+#define DG_MAP_KIND_COVER 2u     /* dg_map_cover */
+#define DG_MAP_KIND_MIN_COVER 3u /* dg_map_min_cover */
+typedef struct {
+  uint32_t at_most;   /* t: a start is specific when its count is in 1..t; 1..0xFFFFFFFD */
+  uint32_t max_count; /* 0 = the cover count, else min(cover, max_count) */
+  uint32_t flags;     /* 0 */
+  uint32_t reserved;  /* 0 */
+} dg_cover_params;
+typedef struct {
+  uint32_t flags;    /* 0 */
+  uint32_t reserved; /* 0 */
+} dg_min_cover_params;
+int dg_map_cover(dg_index* ix, const dg_map* src, const dg_cover_params* p, dg_map** out);
+int dg_map_min_cover(dg_index* ix, const dg_map* src, const dg_min_cover_params* p, dg_map** out);
+/* all zero for a map that neither call made */
+typedef struct {
+  uint32_t kind;            /* DG_MAP_KIND_COVER or DG_MAP_KIND_MIN_COVER */
+  uint32_t k;               /* src's k, or its max_k */
+  uint32_t at_most;         /* 0 for a min-cover map */
+  uint32_t max_count;       /* the clamp the map was made with */
+  uint64_t specific;        /* cover: starts with spec = 1; min-cover: starts with a length */
+  uint64_t covered;         /* positions with a non-zero result */
+  double ms_bits;           /* device time: the bitmap of spec and its rank directory (0 for a min-cover map) */
+  double ms_cover;          /* device time: the per-base kernel */
+  uint64_t transient_bytes; /* HBM held during the transform beside the result */
+} dg_cover_stats_t;
+int dg_map_cover_stats(const dg_map* m, dg_cover_stats_t* out);
 
 /* ABI 7, additive.  Query mappability: the (k,e) counts of dg_mappability_mm for the k-mers of sequences that are NOT in the index (a
  * transcript across an exon-exon junction, a transgene, a viral genome, another allele).  Record i is seqs[off[i] .. off[i+1]), bytes

@@ -25,6 +25,9 @@ ms, probes per valid position, the longest launch -- and beside it the route a b
 t + 1) per k in [a, b], combined on the host; `same_values` compares the two.  With --query-minlen --by-end [--anchor A[,A..]] the call is
 dg_query_min_len_end (the shortest specific k-mer that ENDS at each position, its last A bases exact) and the scan beside it one
 dg_query_map_anchored(k, A, max_count = t + 1) per k, each result shifted by k - 1 to the k-mer's last base on the host.  The CLI run reads names and lengths from a .fai written beside a stub FASTA (it never reads the sequence).
+With --cover [--ks ..] each k gets one dg_mappability(k, max_count 2) call and the dg_map_cover transform of its map (at_most 1): the
+transform's device ms (bitmap and directory, per-base kernel) beside the base call's ms_total of the same process; with --min-cover [--maxk K]
+[--within e] the same for dg_min_unique / dg_min_unique_mm and dg_map_min_cover.
 Prints one JSON line."""
 import argparse, ctypes as C, json, os, re, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,6 +46,8 @@ ap.add_argument("--min-unique", action="store_true", help="time dg_min_unique (m
 ap.add_argument("--maxk", type=int, default=100, help="max_k of --min-unique")
 ap.add_argument("--within", type=int, default=0, help="with --min-unique: e of dg_min_unique_mm (1 or 2), timed beside one dg_mappability_mm(k = --maxk, e) "
                 "pass and the exact dg_min_unique")
+ap.add_argument("--cover", action="store_true", help="time dg_map_cover (per k of --ks, at_most 1) beside the dg_mappability call whose map it transforms")
+ap.add_argument("--min-cover", action="store_true", help="time dg_map_min_cover (max_k = --maxk) beside the dg_min_unique call whose map it transforms")
 ap.add_argument("--query", action="store_true", help="time dg_query_map on a 2 Mb query set (per k of --ks, e = 0, 1, 2) beside dg_count on its k-mers")
 ap.add_argument("--query-mb", type=float, default=1.0, help="Mb of each half of the --query set (cut from the genome / random)")
 ap.add_argument("--anchor", default="", help="with --query: time dg_query_map_anchored at these anchors (comma-separated; k = the k-mer length) beside "
@@ -64,8 +69,8 @@ ap.add_argument("--workdir", default="/dev/shm")
 a = ap.parse_args()
 if a.min_unique and (a.mismatches or a.maxcount):
     ap.error("--min-unique goes with neither --mismatches nor --maxcount")
-if a.within and not a.min_unique:
-    ap.error("--within goes with --min-unique")
+if a.within and not (a.min_unique or a.min_cover):
+    ap.error("--within goes with --min-unique or --min-cover")
 if a.within not in (0, 1, 2):
     ap.error("--within is 0, 1 or 2")
 if a.iupac and not a.query:
@@ -136,6 +141,52 @@ def min_unique_run(fo):
             "exact_pass_k": a.maxk, "exact_pass_ms_total": round(xs.ms_total, 1), "exact_pass_rev_steps": xs.rev_steps,
             "exact_pass_transient_gb": round(xs.transient_bytes / 1e9, 2),
             "cost_in_exact_passes": round(st.ms_total / max(xs.ms_total, 1e-9), 2)}
+
+
+def cover_run(k, fo):
+    """one dg_mappability pass at k (max_count 2: unique or not) and the cover transform of its map, at_most 1"""
+    m, c = C.c_void_p(), C.c_void_p()
+    prm = _capi.MapParams(k, 1 if fo else 0, 2, 0)
+    _capi.check(L, L.dg_mappability(ix.handle, C.byref(prm), C.byref(m)))
+    st = _capi.MapStats()
+    _capi.check(L, L.dg_map_stats(m, C.byref(st)))
+    cp = _capi.CoverParams(1, a.maxcount, 0, 0)
+    t0 = time.time()
+    _capi.check(L, L.dg_map_cover(ix.handle, m, C.byref(cp), C.byref(c)))
+    wall = time.time() - t0
+    L.dg_map_free(m)
+    cs = _capi.CoverStats()
+    _capi.check(L, L.dg_map_cover_stats(c, C.byref(cs)))
+    L.dg_map_free(c)
+    ms = cs.ms_bits + cs.ms_cover
+    return {"cover": True, "k": k, "forward_only": fo, "max_count": a.maxcount, "ms_transform": round(ms, 3), "ms_bits": round(cs.ms_bits, 3),
+            "ms_cover": round(cs.ms_cover, 3), "wall_ms": round(wall * 1e3, 2), "specific": cs.specific, "covered": cs.covered,
+            "transient_gb": round(cs.transient_bytes / 1e9, 3), "gb_per_s": round(8.4 * n / max(ms, 1e-9) / 1e6, 1),
+            "base_ms_total": round(st.ms_total, 1), "transform_over_base": round(ms / max(st.ms_total, 1e-9), 4)}
+
+
+def min_cover_run(fo):
+    """one dg_min_unique pass at max_k = --maxk (--within e: dg_min_unique_mm) and the min-cover transform of its map"""
+    m, c = C.c_void_p(), C.c_void_p()
+    if a.within:
+        prm = _capi.MinUniqueMmParams(a.maxk, a.within, 1 if fo else 0, 0, 0)
+        _capi.check(L, L.dg_min_unique_mm(ix.handle, C.byref(prm), C.byref(m)))
+    else:
+        prm = _capi.MinUniqueParams(a.maxk, 1 if fo else 0, 0, 0)
+        _capi.check(L, L.dg_min_unique(ix.handle, C.byref(prm), C.byref(m)))
+    st = _capi.MapStats()
+    _capi.check(L, L.dg_map_stats(m, C.byref(st)))
+    cp = _capi.MinCoverParams(0, 0)
+    t0 = time.time()
+    _capi.check(L, L.dg_map_min_cover(ix.handle, m, C.byref(cp), C.byref(c)))
+    wall = time.time() - t0
+    L.dg_map_free(m)
+    cs = _capi.CoverStats()
+    _capi.check(L, L.dg_map_cover_stats(c, C.byref(cs)))
+    L.dg_map_free(c)
+    return {"min_cover": True, "max_k": a.maxk, "within": a.within, "forward_only": fo, "ms_transform": round(cs.ms_cover, 3), "wall_ms": round(wall * 1e3, 2),
+            "with_length": cs.specific, "covered": cs.covered, "gb_per_s": round(9.0 * n / max(cs.ms_cover, 1e-9) / 1e6, 1),
+            "base_ms_total": round(st.ms_total, 1), "transform_over_base": round(cs.ms_cover / max(st.ms_total, 1e-9), 4)}
 
 
 def min_unique_mm_run(fo):
@@ -486,6 +537,12 @@ elif a.query:
         else:
             query_runs(k, recs)
     ks = []
+elif a.cover or a.min_cover:
+    for fo in STRANDS:
+        for k in ([int(x) for x in a.ks.split(",")] if a.cover else [a.maxk]):
+            runs.append(cover_run(k, fo) if a.cover else min_cover_run(fo))
+            print(json.dumps(runs[-1]), file=sys.stderr, flush=True)
+    ks = []
 elif a.min_unique:
     for fo in STRANDS:
         runs.append(min_unique_mm_run(fo) if a.within else min_unique_run(fo))
@@ -529,7 +586,7 @@ ix.close()
 # the CLI end to end: open + map + runs + format + gzip
 stem = os.path.join(a.workdir, "dicey_map_bench_cli_%s" % a.genome)
 gz = stem + ".bedgraph.gz"
-if a.cli_k and not a.min_unique and not a.query and not a.query_minlen:
+if a.cli_k and not a.min_unique and not a.cover and not a.min_cover and not a.query and not a.query_minlen:
     with open(stem + ".fa", "w") as f:
         f.write(">chr1\nN\n")
     with open(stem + ".fa.fai", "w") as f:
